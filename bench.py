@@ -8,7 +8,13 @@ quantised observations already resident in HBM.  Default workload = the metric c
 quantiser, SNR 5 dB, mode 'all', B=100,000 observations, FP64 arithmetic (the reference's complex128).
 
   python bench.py [--gpus N --steps K --warmup W] [--config metric|cfg1..cfg5|cfg3dense|cfg5dense]
-                  [--shard batch|k] [--precision f64|fast] [--chunks C]
+                  [--shard batch|k] [--precision f64|fast] [--chunks C] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (throughput, ms_per_step, the MSE against
+the true channels and the roofline of the timed kernel, all from the timed steps themselves).  ``--full`` adds the legs
+that take runs of their own: the CPU baseline, the parity leg against the FP64 oracle, the fast-path side line and
+(``--dropin``) the drop-in side line.  ``--dump-outputs DIR`` writes the estimates of the last timed step to
+``DIR/h_hat.npy``.
 
 Multi-GPU: one process per GPU.  ``--gpus N`` without a torch.distributed launcher starts the N ranks
 itself (child processes, before any GPU call); under ``torch.distributed.run`` the ranks come from the
@@ -80,12 +86,21 @@ def parse():
                     help="K-shard SUM collective: reduce-scatter (rank keeps its rows) or all-reduce")
     ap.add_argument("--single-buffer", action="store_true",
                     help="native K-shard: one table set (no overlap of the next prepare with the current step)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU-baseline budget per leg (0 = skip)")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fast-path side line")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the CPU baseline (--cpu-seconds), the parity leg against the FP64 "
+                         "oracle (--no-parity), the fast-path side line (--no-extras) and, on request, the drop-in side "
+                         "line (--dropin).  Without --full none of them runs: set up, warm up, time the steps, print")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/h_hat.npy: float64 "
+                         "(rows, N, 2) = (re, im) of the estimates; beyond DUMP_MAX_BYTES a fixed seeded sample of the "
+                         "rows (the inputs are seeded, so two builds can be compared output for output)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0,
+                    help="with --full: CPU-baseline budget per leg (0 = skip)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the fast-path side line")
     ap.add_argument("--dropin", action="store_true",
-                    help="add the drop-in (numpy host I/O) side line; off by default because its chunked launches of "
-                         "the headline kernel would enter a rocprof kernel-stats average of the bench command")
+                    help="with --full: add the drop-in (numpy host I/O) side line; off by default because its chunked "
+                         "launches of the headline kernel would enter a rocprof kernel-stats average of the bench command")
     ap.add_argument("--mean", action="store_true",
                     help="components with non-zero means (0.3 x CN(0, 1) per entry, seeded): the reference's fit "
                          "default zero_mean=False (gmm_cplx_bussgang.py:96-100); the bench configs are zero-mean")
@@ -100,6 +115,10 @@ def parse():
                     help="JSON with PMC-derived HBM bytes per launch of the estimate kernel "
                          "(default profiles/traffic_<config>.json, traffic_<config>_mean.json with --mean)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:  # a plain run measures the headline figure only
+        a.cpu_seconds, a.no_parity, a.no_extras, a.dropin = 0.0, True, True, False
     if a.shard is None:
         a.shard = DEFAULT_SHARD[a.config]
     return a
@@ -186,6 +205,29 @@ def make_inputs(cfg, seed, pool=2048):
     y = inputs.get_observation_nbit(h, cfg["snr"], None, cfg["n_bits"], quantizer[0], quantizer[1],
                                     rng=np.random.default_rng(2000 + seed))
     return means, covs, w, h, np.ascontiguousarray(y, dtype=np.complex128), quantizer
+
+
+# ------------------------------------------------------------------------------------------ output dump
+DUMP_MAX_BYTES = 32 << 20  # per array; a whole dump stays well below 64 MB
+
+
+def dump_outputs(path, hg):
+    """--dump-outputs: the complex128 estimates hg (rows, N) of the last timed step as path/h_hat.npy, float64
+    (rows, N, 2) = (re, im).  More than DUMP_MAX_BYTES: a fixed seeded sample of the rows, in ascending order (the
+    same rows in every run of the same arguments).  Returns what the result line says about the dump."""
+    os.makedirs(path, exist_ok=True)
+    hg = np.ascontiguousarray(hg, dtype=np.complex128)
+    n, N = hg.shape
+    keep = max(1, DUMP_MAX_BYTES // (16 * N))
+    rows = "all"
+    if n > keep:
+        sel = np.sort(np.random.default_rng(4242).choice(n, size=keep, replace=False))
+        hg = np.ascontiguousarray(hg[sel])
+        rows = f"{keep} of {n}: sorted default_rng(4242).choice({n}, {keep}, replace=False)"
+    arr = hg.view(np.float64).reshape(hg.shape[0], N, 2)
+    np.save(os.path.join(path, "h_hat.npy"), arr)
+    return {"h_hat.npy": {"dtype": "float64", "shape": list(arr.shape), "layout": "(row, antenna, re/im)",
+                          "rows": rows}}
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -483,7 +525,8 @@ SWEEP_SNRS = [-10, -5, 0, 5, 10, 15, 20]  # Bussgang_GMM.py:43
 
 def sweep_main(args):
     """--sweep: the reference's SNR loop on one GPU, one batch per SNR point, prepare + estimate per point; the
-    double-buffered SnrSweep against the serial loop on one model.  One JSON line."""
+    double-buffered SnrSweep against the serial loop on one model.  One JSON line; its parity entry (the 5 dB point
+    against the FP64 oracle) is filled with --full."""
     import torch
     from quantized_channel_estimation_amd import _lib
     from quantized_channel_estimation_amd.sweep import SnrSweep
@@ -709,8 +752,11 @@ def main():
     ho = None
     n_chk = min(B, 512)
     rows, hres = res
+    dumped = None
     if rank == 0:
         hg = hres.cpu().numpy()
+        if args.dump_outputs:  # rank 0's result of the last timed step (K-shard reduce-scatter: its rows of the batch)
+            dumped = dump_outputs(args.dump_outputs, hg)
         idx = np.arange(B) if rows is None else rows.cpu().numpy()
         mse = float(np.mean(np.abs(hg - h[idx]) ** 2))
         if not args.no_parity:
@@ -786,6 +832,8 @@ def main():
             "cpu_baseline": cpu,
         }
         line.update(extras)
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     # explicit teardown while every rank and the runtimes are still here (not left to exit-time destructors)
     torch.cuda.synchronize(dev)

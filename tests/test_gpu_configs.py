@@ -141,7 +141,8 @@ def test_bench_kshard_two_ranks_gloo_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--batch", "4096", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-extras"],
+                        "--batch", "4096", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "0",
+                        "--no-extras"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]

@@ -320,7 +320,7 @@ def test_bench_sweep_line():
     import sys
     from conftest import ROOT
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg1", "--sweep", "--steps", "3",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=240)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert r["config"]["points"] == 7 and r["max_rel_dev_vs_serial"] < 1e-12

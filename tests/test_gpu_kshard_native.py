@@ -455,7 +455,7 @@ def test_bench_native_two_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup",
-                        "2", "--batch", "20000", "--cpu-seconds", "0", "--no-extras"], env=env, capture_output=True,
+                        "2", "--batch", "20000", "--full", "--cpu-seconds", "0", "--no-extras"], env=env, capture_output=True,
                        text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
