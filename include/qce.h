@@ -246,6 +246,18 @@ int qce_rate_bound(const double* h_est, const double* h, int64_t B, int N, const
 int qce_rate_mf(const double* h_est, const double* h, int64_t B, int N, const double* buss, const double* Cq,
                 double* out, int device, int io, void* stream);
 
+/* VAE-parameterised Bussgang LMMSE (estimators/vae.py:376-431 convert_dec_outputs with zeromean=True, then
+ * :368-369 lmmse), model-free: per sample the decoder's log-variances logvar (B,N) (float when logvar_is_f32,
+ * else double) give the circulant Ch = F^H diag(max(exp(-logvar), 1e-12)) F; with the pilot matrix
+ * A = kron(x, I_N), x_cplx (P,) c128 host array, the conversion and the LMMSE run in the Fourier domain (N-point
+ * transforms and a P x P Cholesky per DFT bin, csrc/qce_vae.hip).  y (B, P N) c128 pilot-major -> h_out (B,N) c128.
+ * n_bits: 1, 2..16 (uniform quantiser) or +INFINITY.  N: a power of two in [16, 256], P <= 4, else QCE_ENOTIMPL.
+ * logvar / y / h_out where `io` says; B of any size (chunked internally); `stream` NULL = the null stream of
+ * `device`.  The call synchronises the stream to read the status: QCE_ECHOL if some bin's P x P matrix is not
+ * positive definite (the reference's pinv is not emulated). */
+int qce_vae_estimate(int N, int P, const double* x_cplx, double snr_db, double n_bits, const void* logvar,
+                     int logvar_is_f32, const double* y, int64_t B, double* h_out, int io, int device, void* stream);
+
 /* Page-locked host memory (hipHostMalloc / hipHostFree).  QCE_IO_HOST calls DMA straight from / into page-locked
  * arrays (and from / into pageable ones they can register for the call): a caller that allocates its result arrays
  * here, and reuses them, saves the page faults of fresh pageable memory (the Python layer's result pool, _lib.py). */

@@ -2094,6 +2094,89 @@ int qce_rate_mf(const double* h_est, const double* h, int64_t B, int N, const do
   return QCE_OK;
 }
 
+int qce_vae_estimate(int N, int P, const double* x_cplx, double snr_db, double n_bits, const void* logvar,
+                     int logvar_is_f32, const double* y, int64_t B, double* h_out, int io, int device, void* stream) {
+  if (N < 1 || P < 1 || B < 0 || !x_cplx) return fail(QCE_EARG, "vae_estimate: bad shape");
+  if (io != QCE_IO_HOST && io != QCE_IO_DEVICE) return fail(QCE_EARG, "vae_estimate: bad io");
+  if (B > 0 && (!logvar || !y || !h_out)) return fail(QCE_EARG, "vae_estimate: null buffer");
+  if (N < 16 || N > 256 || (N & (N - 1)))
+    return fail(QCE_ENOTIMPL, "vae_estimate: n_antennas must be a power of two in [16, 256], got " + std::to_string(N));
+  if (P > QCE_VAE_MAX_PILOTS)
+    return fail(QCE_ENOTIMPL, "vae_estimate: at most " + std::to_string(QCE_VAE_MAX_PILOTS) + " pilots, got " +
+                                  std::to_string(P));
+  QceVaeArgs a;
+  a.N = N;
+  a.P = P;
+  a.n_bits = 0;
+  a.delta = 0.0;
+  if (n_bits == 1.0) a.kind = 0;
+  else if (isinf(n_bits) && n_bits > 0) a.kind = 2;
+  else {
+    a.kind = 1;
+    a.n_bits = (int)n_bits;
+    if (!(n_bits >= 2.0) || (double)a.n_bits != n_bits) return fail(QCE_EARG, "vae_estimate: n_bits must be an integer >= 1 or inf");
+    if (a.n_bits > QCE_MAX_UNIFORM_BITS)
+      return fail(QCE_ENOTIMPL, "vae_estimate: uniform quantisers up to " + std::to_string(QCE_MAX_UNIFORM_BITS) + " bits");
+    a.delta = uniform_step(snr_db, a.n_bits);
+  }
+  // the reference builds these constants from torch.tensor(np.pi), a float32 tensor (vae.py:403, :410,
+  // uniform_quantizer.py:79, :86)
+  const float pi_f = (float)M_PI;
+  a.k1 = (double)sqrtf(2.0f / pi_f);
+  a.k2 = (double)((float)a.delta / sqrtf(pi_f));
+  a.k3 = (double)(2.0f / pi_f);
+  a.s2 = pow(10.0, -snr_db / 10.0);
+  for (int p = 0; p < QCE_VAE_MAX_PILOTS; ++p)
+    a.x[p] = p < P ? make_double2(x_cplx[2 * p], x_cplx[2 * p + 1]) : make_double2(0.0, 0.0);
+  a.lv_f32 = logvar_is_f32 ? 1 : 0;
+  a.TS = 0;
+  if (B == 0) return QCE_OK;
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lvb = logvar_is_f32 ? sizeof(float) : sizeof(double);
+  const int64_t CH = 1 << 16;  // samples per launch (and per staging buffer for host I/O)
+  int status = 0;
+  {
+    StreamScratch sc(st);
+    void *dstat, *dlv = nullptr, *dy = nullptr, *dh = nullptr;
+    HIPCHK(sc.get(&dstat, sizeof(int)));
+    HIPCHK(hipMemsetAsync(dstat, 0, sizeof(int), st));
+    a.status = (int*)dstat;
+    const int64_t cmax = B < CH ? B : CH;
+    if (io == QCE_IO_HOST) {
+      HIPCHK(sc.get(&dlv, lvb * (size_t)cmax * N));
+      HIPCHK(sc.get(&dy, sizeof(double2) * (size_t)cmax * P * N));
+      HIPCHK(sc.get(&dh, sizeof(double2) * (size_t)cmax * N));
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += CH) {
+      const int64_t nb = B - b0 < CH ? B - b0 : CH;
+      const char* lv_c = (const char*)logvar + lvb * (size_t)b0 * N;
+      const double* y_c = y + 2 * (size_t)b0 * P * N;
+      double* h_c = h_out + 2 * (size_t)b0 * N;
+      a.B = nb;
+      if (io == QCE_IO_HOST) {
+        HIPCHK(hipMemcpyAsync(dlv, lv_c, lvb * (size_t)nb * N, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dy, y_c, sizeof(double2) * (size_t)nb * P * N, hipMemcpyHostToDevice, st));
+        a.lv = dlv;
+        a.y = (const double2*)dy;
+        a.h = (double2*)dh;
+      } else {
+        a.lv = lv_c;
+        a.y = (const double2*)y_c;
+        a.h = (double2*)h_c;
+      }
+      HIPCHK(qce_launch_vae(a, st));
+      if (io == QCE_IO_HOST) HIPCHK(hipMemcpyAsync(h_c, dh, sizeof(double2) * (size_t)nb * N, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipMemcpyAsync(&status, dstat, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  if (status)
+    return fail(QCE_ECHOL, "vae_estimate: the quantised-observation covariance Cr is not positive definite in some "
+                           "DFT bin (the reference's pinv has no counterpart here)");
+  return QCE_OK;
+}
+
 }  // extern "C"
 
 // Selective-mode LMMSE sum with weights computed elsewhere (the K-shard path's globally selected weights of

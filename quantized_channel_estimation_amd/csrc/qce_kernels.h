@@ -306,6 +306,24 @@ int qce_rate_scratch();
 hipError_t qce_launch_rate(long long B, int N, const double2* he, const double2* h, const double* buss,
                            const double2* Cq, double clip, double2* inner, double* den2, double* part, double* stat,
                            hipStream_t st);
+// VAE-parameterised Bussgang LMMSE in the Fourier domain (qce_vae.hip; estimators/vae.py:368-431)
+#define QCE_VAE_MAX_PILOTS 4
+#define QCE_VAE_LDS_BUDGET (72 * 1024)  // LDS per workgroup: two workgroups per CU
+struct QceVaeArgs {
+  long long B;
+  int N, P;           // N a power of two in [16, 256], P <= QCE_VAE_MAX_PILOTS
+  int kind, n_bits;   // 0: 1 bit, 1: uniform n_bits, 2: no quantisation
+  double s2, delta;   // noise variance, uniform quantiser step
+  double k1, k2, k3;  // the reference's float32 constants sqrt(2/pi), delta/sqrt(pi), 2/pi
+  double2 x[QCE_VAE_MAX_PILOTS];  // pilot vector: A = kron(x, I_N)
+  const void* lv;     // B x N log-variances, float (lv_f32) or double
+  int lv_f32;
+  const double2* y;   // B x (P N), pilot-major
+  double2* h;         // B x N
+  int* status;        // |= 1 when some bin's P x P matrix is not positive definite
+  int TS;             // samples per workgroup (set by the launcher)
+};
+hipError_t qce_launch_vae(const QceVaeArgs& a, hipStream_t st);
 // Bussgang LS with column-orthogonal A_eff (qce_genie.hip; estimators/LS.py)
 hipError_t qce_launch_ls(long long B, int N, int M, const double2* y, const long long* comp, const double2* Aeff,
                          double2* h, hipStream_t st);
