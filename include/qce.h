@@ -301,6 +301,10 @@ int qce_comm_info(qce_comm* comm, int* rank, int* world, int* device, int* kind)
 
 /* Components [lo, hi) of rank `rank` in the balanced contiguous split of K over `world` ranks (K >= world). */
 int qce_kshard_slice(int K, int world, int rank, int* lo, int* hi);
+/* (world, rank) a K-shard's rows are laid out for: the communicator's, or on a world-1 communicator the test hook
+ * QCE_KSHARD_EMULATE_WORLD="W[:R]" (2 <= W <= 4096, 0 <= R < W; anything else is ignored) that qce_kshard_create
+ * applies.  Host-only: needs no GPU. */
+int qce_kshard_layout(int world, int rank, int* layout_world, int* layout_rank);
 /* Rows of h_out a rank receives from qce_kshard_estimate: per pipeline chunk the global row range
  * [ranges[2i], ranges[2i+1]) (concatenated in h_out in this order); scatter = 0: every rank gets all B rows.
  * `cap` = number of ranges the array holds; *n = ranges written.  Selective modes use chunks = 1. */

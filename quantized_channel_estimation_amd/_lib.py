@@ -27,7 +27,7 @@ COMM_RCCL, COMM_HOST = 0, 1
 COLL_ALLREDUCE_SUM, COLL_ALLREDUCE_MAX, COLL_REDUCE_SCATTER_SUM, COLL_ALLGATHER = range(4)
 
 # The reference's message for a non-positive-definite Cr_k (gmm_cplx_bussgang.py:33-37, raised at :43-46); the
-# library returns the same text with QCE_ECHOL (csrc/qce_capi.hip check_status), the K-shard path raises it from
+# library returns the same text with QCE_ECHOL (csrc/qce_capi_prepare.hip check_status), the K-shard path raises it from
 # the flag its shift carries (sharding.py).
 CHOL_MESSAGE = ("Fitting the mixture model failed because some components have ill-defined empirical covariance "
                 "(for instance caused by singleton or collapsed samples). Try to decrease the number of "
@@ -95,6 +95,8 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "qce_kshard_slice": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                         ctypes.POINTER(ctypes.c_int)]),
+    "qce_kshard_layout": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int)]),
     "qce_kshard_rows": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "qce_kshard_create": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.POINTER(_vp)]),
@@ -549,17 +551,9 @@ def kshard_slice(K, world, rank):
 def kshard_layout(world, rank):
     """(world, rank) a K-shard's rows are laid out for: the communicator's, or on a world-1 communicator the test hook
     QCE_KSHARD_EMULATE_WORLD="W[:R]" (one GPU rehearsing rank R of a W-GPU step; csrc/qce_kshard.hip)."""
-    e = os.environ.get("QCE_KSHARD_EMULATE_WORLD", "")
-    if world != 1 or not e:
-        return world, rank
-    try:
-        w, _, r = e.partition(":")
-        w, r = int(w), int(r or 0)
-    except ValueError:
-        return world, rank
-    if w < 2 or w > 4096 or not 0 <= r < w:
-        return world, rank
-    return w, r
+    w, r = ctypes.c_int(), ctypes.c_int()
+    check(load().qce_kshard_layout(int(world), int(rank), ctypes.byref(w), ctypes.byref(r)))
+    return w.value, r.value
 
 
 def kshard_rows(B, chunks, world, rank, scatter):

@@ -12,10 +12,8 @@
 // Work per estimate: 8 K M^2 + 8 K M N real flops on FP64 MFMA, the same count as the fused kernels'.
 #include <math.h>
 
-#include "../../include/qce.h"
+#include "qce_capi.h"
 #include "qce_common.h"
-#include "qce_kernels.h"
-#include "qce_model.h"
 
 namespace {
 
@@ -137,19 +135,13 @@ long long chunk_rows(const qce_model* m, long long B) {
 
 }  // namespace
 
-#define BIG_HIP(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return qce_set_error(QCE_EHIP, std::string(#expr) + " failed: " + hipGetErrorString(e_)); \
-  } while (0)
-
 // Wstack of the current prepare (lazily, once per prepare)
 int qce_big_prepare_filters(qce_model* m, hipStream_t st) {
   if (m->big_ws_valid) return QCE_OK;
-  BIG_HIP(m->big_ws.ensure((size_t)m->K * m->N * m->M));
+  HIPCHK(m->big_ws.ensure((size_t)m->K * m->N * m->M));
   hipLaunchKernelGGL(k_big_stack, dim3(grid_n((long long)m->K * m->N * m->M)), dim3(256), 0, st, m->K, m->N, m->M,
                      m->W.p, m->big_ws.p);
-  BIG_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   m->big_ws_valid = 1;
   return QCE_OK;
 }
@@ -157,16 +149,16 @@ int qce_big_prepare_filters(qce_model* m, hipStream_t st) {
 int qce_big_lp(qce_model* m, const double2* y, long long B, double* lp, hipStream_t st) {
   const int K = m->K, M = m->M;
   const long long C = chunk_rows(m, B);
-  BIG_HIP(m->big_d.ensure((size_t)K * C * M));
+  HIPCHK(m->big_d.ensure((size_t)K * C * M));
   const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
   for (long long r0 = 0; r0 < B; r0 += C) {
     const long long n = (B - r0) < C ? (B - r0) : C;
     // D_k (n x M) = Y (n x M) . Linv_k^T
-    BIG_HIP(qce_zgemm_batched(0, 1, (int)n, M, M, one, y + r0 * M, M, 0, m->Linv.p, M, (long long)M * M, zero,
+    HIPCHK(qce_zgemm_batched(0, 1, (int)n, M, M, one, y + r0 * M, M, 0, m->Linv.p, M, (long long)M * M, zero,
                               m->big_d.p, M, n * M, K, st));
     hipLaunchKernelGGL(k_big_lp, dim3((unsigned)((n * K + 3) / 4)), dim3(256), 0, st, n, K, M, m->big_d.p, m->q0.p,
                        m->cconst.p, lp + r0 * K);
-    BIG_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   return QCE_OK;
 }
@@ -177,18 +169,18 @@ int qce_big_wsum(qce_model* m, const double2* y, long long B, const double* w, d
   const int K = m->K, M = m->M, N = m->N;
   if (int rc = qce_big_prepare_filters(m, st)) return rc;
   const long long C = chunk_rows(m, B);
-  BIG_HIP(m->big_d.ensure((size_t)K * C * M));
+  HIPCHK(m->big_d.ensure((size_t)K * C * M));
   const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
   for (long long r0 = 0; r0 < B; r0 += C) {
     const long long n = (B - r0) < C ? (B - r0) : C;
     hipLaunchKernelGGL(k_big_scale, dim3(grid_n(n * K * M)), dim3(256), 0, st, n, K, M, y + r0 * M, w + r0 * K,
                        m->big_d.p);
-    BIG_HIP(hipGetLastError());
-    BIG_HIP(qce_zgemm_batched(0, 1, (int)n, N, K * M, one, m->big_d.p, K * M, 0, m->big_ws.p, K * M, 0, zero,
+    HIPCHK(hipGetLastError());
+    HIPCHK(qce_zgemm_batched(0, 1, (int)n, N, K * M, one, m->big_d.p, K * M, 0, m->big_ws.p, K * M, 0, zero,
                               out + r0 * ldo, (int)ldo, 0, 1, st));
     hipLaunchKernelGGL(k_big_bias, dim3(grid_n(n * N)), dim3(256), 0, st, n, K, N, w + r0 * K, m->bvec.p,
                        out + r0 * ldo, ldo);
-    BIG_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   return QCE_OK;
 }
@@ -197,7 +189,7 @@ int qce_big_wsum(qce_model* m, const double2* y, long long B, const double* w, d
 int qce_big_proba(qce_model* m, long long B, hipStream_t st) {
   hipLaunchKernelGGL(k_big_weights, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, B, m->K, m->lp_scr.p, 3, nullptr,
                      m->w64_scr.p, nullptr, nullptr, nullptr, 0LL);
-  BIG_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return QCE_OK;
 }
 
@@ -205,12 +197,12 @@ int qce_big_proba(qce_model* m, long long B, hipStream_t st) {
 int qce_big_partial(qce_model* m, const double2* y, long long B, int wmode, double* om, double* os, double* oa,
                     double* pk, const double* shift, hipStream_t st) {
   const int K = m->K, N = m->N;
-  BIG_HIP(m->lp_scr.ensure((size_t)B * K));
-  BIG_HIP(m->w64_scr.ensure((size_t)B * K));
+  HIPCHK(m->lp_scr.ensure((size_t)B * K));
+  HIPCHK(m->w64_scr.ensure((size_t)B * K));
   if (int rc = qce_big_lp(m, y, B, m->lp_scr.p, st)) return rc;
   hipLaunchKernelGGL(k_big_weights, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, B, K, m->lp_scr.p, wmode, shift,
                      m->w64_scr.p, om, os, pk, 2LL * N + 2);
-  BIG_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (wmode == 1) return qce_big_wsum(m, y, B, m->w64_scr.p, reinterpret_cast<double2*>(oa), N, st);
   return qce_big_wsum(m, y, B, m->w64_scr.p, reinterpret_cast<double2*>(pk) + 1, N + 1, st);
 }

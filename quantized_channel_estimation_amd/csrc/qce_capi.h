@@ -1,0 +1,72 @@
+// Private header of the C-ABI host units (qce_capi*.hip, qce_kshard.hip, qce_big.hip): the error slot, the HIP
+// check macro and the device guard they all use, then the helpers the qce_capi*.hip units share.
+#pragma once
+#include <string>
+
+#include "../../include/qce.h"
+#include "qce_kernels.h"
+#include "qce_model.h"
+
+int qce_set_error(int code, const std::string& msg);  // sets qce_last_error() and returns code
+
+#define HIPCHK(expr)                                                                               \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess)                                                                          \
+      return qce_set_error(QCE_EHIP, std::string(#expr) + " failed: " + hipGetErrorString(e_));    \
+  } while (0)
+
+// Makes `dev` the calling thread's device for one C-ABI call and puts the caller's back at its end.
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev && hipSetDevice(dev) != hipSuccess) (void)hipGetLastError();  // no sticky error left behind
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// shared by the qce_capi*.hip units
+// ---------------------------------------------------------------------------------------------------------------
+inline hipStream_t pick_stream(qce_model* m, void* stream) { return stream ? (hipStream_t)stream : m->stream; }
+
+// qce_capi_prepare.hip
+hipError_t detect_structure(qce_model* m);  // at creation / set_params: is the mixture (block-)circulant?
+int check_status(qce_model* m, bool block);  // the last prepare's Cholesky status, once it is known (block: wait)
+int check_model(qce_model* m, bool need_prepared);
+int ensure_dense(qce_model* m, void* stream = nullptr);  // dense tables of a prepare that took the Fourier path
+double uniform_step(double snr_db, int nb);
+
+#define HOST_SYNC_CHECK(m, st)                         \
+  do {                                                 \
+    HIPCHK(hipStreamSynchronize(st));                  \
+    if (int rc_ = check_status((m), true)) return rc_; \
+  } while (0)
+
+// qce_capi_estimate.hip
+// Arithmetic of the dense 'all' / partial path for this model: the model option, overridden by
+// QCE_KERNEL=f64 | h2 | f32 (A/B runs).
+bool want_f64(const qce_model* m);
+QceFftEstArgs fft_args(qce_model* m, const double2* y, long long B);
+// stage host input (io == HOST) or use the device pointer directly
+int stage_input(qce_model* m, const double* y, long long B, int io, hipStream_t st, const double2** dy);
+// lp (B x K) of the prepared model on the family's log-prob kernel
+int backend_lp(qce_model* m, const double2* x, long long B, double* lp, hipStream_t st);
+
+#ifdef QCE_STAMPS
+// qce_capi_debug.hip (diagnostic build): segment cycles of the last FP64 launch
+extern unsigned long long* g_f64_stamps;
+extern long long g_f64_stamp_records;
+#endif
+
+// qce_capi_hostio.hip
+// rows per host-pipeline chunk; 0 = one shot (QCE_HOST_PIPELINE=0, or too small a batch to split)
+long long host_chunk_rows(const qce_model* m, long long B);
+int estimate_host_chunked(qce_model* m, const double* y, long long B, long long C, int mode, double mode_param,
+                          double* h_out, hipStream_t st);

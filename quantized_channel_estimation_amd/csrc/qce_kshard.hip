@@ -30,9 +30,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/qce.h"
+#include "qce_capi.h"
 #include "qce_common.h"
-#include "qce_model.h"
 
 namespace {
 
@@ -45,30 +44,11 @@ const char* kCholMessage =
     "(for instance caused by singleton or collapsed samples). Try to decrease the number of "
     "components, or increase reg_covar.";
 
-#define KS_HIP(expr)                                                                               \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return qce_set_error(QCE_EHIP, std::string(#expr) + " failed: " + hipGetErrorString(e_));    \
-  } while (0)
-
 #define KS_RC(expr)             \
   do {                          \
     int rc_ = (expr);           \
     if (rc_ != QCE_OK) return rc_; \
   } while (0)
-
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev && hipSetDevice(dev) != hipSuccess) (void)hipGetLastError();  // no sticky error left behind
-  }
-  ~DevGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 struct Chunk {
   long long lo, hi;    // global rows of the chunk
@@ -366,26 +346,6 @@ __global__ __launch_bounds__(256) void k_ks_slice(long long B, int K, int lo, in
   }
 }
 
-template <typename T>
-struct KBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    hipError_t e = hipMalloc(&p, sizeof(T) * (count ? count : 1));
-    if (e == hipSuccess) n = count;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
 }  // namespace
 
 struct qce_comm {
@@ -418,20 +378,20 @@ struct qce_kshard {
   hipStream_t cs = nullptr;  // communication stream: the chunks' collectives and row finalisation
   std::vector<hipEvent_t> ev_chunk;
   hipEvent_t ev_done = nullptr;
-  KBuf<double> shift, fl, earlier, rs;  // shift: one slot per table set
-  KBuf<double> pkb[2];                  // the steps' send rows, alternating: step t+1's kernels fill one while step
+  DevBuf<double> shift, fl, earlier, rs;  // shift: one slot per table set
+  DevBuf<double> pkb[2];                  // the steps' send rows, alternating: step t+1's kernels fill one while step
   int pkp = 0;                          // t's collectives still read the other
-  KBuf<double> step_shift;              // [2 parity + 0]: the shard's shift M_r the step's kernels used (copied on the
+  DevBuf<double> step_shift;              // [2 parity + 0]: the shard's shift M_r the step's kernels used (copied on the
                                         // compute stream); [2 parity + 1]: the agreed M* (MAX on the comm stream)
-  KBuf<double> scale;                   // [parity]: e^{M_r - M*}, the PreMulSum scalar of the step's SUMs
-  KBuf<double> probe;                   // PreMulSum reduce-scatter check: [scalar, mismatch flag]
+  DevBuf<double> scale;                   // [parity]: e^{M_r - M*}, the PreMulSum scalar of the step's SUMs
+  DevBuf<double> probe;                   // PreMulSum reduce-scatter check: [scalar, mismatch flag]
   std::vector<std::pair<long long, int>> rs_premul;  // (count, RCCL's PreMulSum reduce-scatter exact at that count)
   hipEvent_t ev_pk[2] = {nullptr, nullptr};  // recorded on cs after the last reader of pkb[p] / step_shift[p]
   int pk_valid[2] = {0, 0};
   hipEvent_t ev_st2cs = nullptr, ev_cs2st = nullptr;
   hipEvent_t ev_shift_read = nullptr;  // recorded on cs once a step has read its table set's shift slot (agree_shift)
   int shift_read_valid = 0;
-  KBuf<unsigned> cnt;
+  DevBuf<unsigned> cnt;
   double* host_fl = nullptr;  // pinned: [fl0, fl1, earlier0, earlier1] of the last step
   double last_flags[4] = {0, 0, 0, 0};  // host_fl as the last qce_kshard_finish read it
   int local_chol = 0;         // this rank's library refused a call with the reference's Cholesky error
@@ -447,7 +407,7 @@ struct qce_kshard {
   } pending;
   int any_pending_before = 0;  // a step was superseded before finish(): its flags went into `earlier`
   // repair / selective-mode scratch
-  KBuf<double> rm, rsum, racc, mg, lp, lpad, gath, lpfull, wfull, wloc;
+  DevBuf<double> rm, rsum, racc, mg, lp, lpad, gath, lpfull, wfull, wloc;
   // kernel timing
   int timing = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
@@ -498,28 +458,28 @@ int collective(qce_comm* c, int op, double* send, double* recv, long long count,
   const long long nr = (op == QCE_COLL_ALLGATHER) ? count * c->world : count;
   if (premul && sum) {
     hipLaunchKernelGGL(k_ks_scale_rows, dim3(grid_for(ns)), dim3(256), 0, st, ns, send, premul);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   if ((size_t)ns > c->pin_cap_send) {
     if (c->pin_send) (void)hipHostFree(c->pin_send);
     c->pin_send = nullptr;
     c->pin_cap_send = 0;
-    KS_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->pin_send), sizeof(double) * ns, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->pin_send), sizeof(double) * ns, hipHostMallocDefault));
     c->pin_cap_send = (size_t)ns;
   }
   if ((size_t)nr > c->pin_cap_recv) {
     if (c->pin_recv) (void)hipHostFree(c->pin_recv);
     c->pin_recv = nullptr;
     c->pin_cap_recv = 0;
-    KS_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->pin_recv), sizeof(double) * nr, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->pin_recv), sizeof(double) * nr, hipHostMallocDefault));
     c->pin_cap_recv = (size_t)nr;
   }
-  KS_HIP(hipMemcpyAsync(c->pin_send, send, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
-  KS_HIP(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(c->pin_send, send, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   if (c->fn(c->user, op, c->pin_send, c->pin_recv, count) != 0)
     return qce_set_error(QCE_ECOMM, "host collective failed");
-  KS_HIP(hipMemcpyAsync(recv, c->pin_recv, sizeof(double) * nr, hipMemcpyHostToDevice, st));
-  KS_HIP(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(recv, c->pin_recv, sizeof(double) * nr, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
   return QCE_OK;
 }
 
@@ -554,16 +514,16 @@ int timed_begin(qce_kshard* ks, hipStream_t st) {
   if (!ks->timing) return QCE_OK;
   if (ks->tev_used == ks->tev.size()) {
     hipEvent_t a, b;
-    KS_HIP(hipEventCreate(&a));
-    KS_HIP(hipEventCreate(&b));
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
     ks->tev.emplace_back(a, b);
   }
-  KS_HIP(hipEventRecord(ks->tev[ks->tev_used].first, st));
+  HIPCHK(hipEventRecord(ks->tev[ks->tev_used].first, st));
   return QCE_OK;
 }
 int timed_end(qce_kshard* ks, hipStream_t st) {
   if (!ks->timing) return QCE_OK;
-  KS_HIP(hipEventRecord(ks->tev[ks->tev_used].second, st));
+  HIPCHK(hipEventRecord(ks->tev[ks->tev_used].second, st));
   ks->tev_used++;
   return QCE_OK;
 }
@@ -578,18 +538,18 @@ int rs_premul_exact(qce_kshard* ks, double* send, double* recv, long long count,
       return QCE_OK;
     }
   qce_comm* c = ks->c;
-  KS_HIP(ks->probe.ensure(2));
+  HIPCHK(ks->probe.ensure(2));
   const long long n = count * c->world;
   hipLaunchKernelGGL(k_ks_probe_fill, dim3(grid_for(n)), dim3(256), 0, ks->cs, send, n, ks->probe.p);
-  KS_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   KS_RC(collective(c, QCE_COLL_REDUCE_SCATTER_SUM, send, recv, count, ks->cs, ks->probe.p));
   hipLaunchKernelGGL(k_ks_probe_check, dim3(grid_for(count)), dim3(256), 0, ks->cs, recv, count, c->world, c->rank,
                      ks->probe.p + 1);
-  KS_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   KS_RC(collective(c, QCE_COLL_ALLREDUCE_MAX, ks->probe.p + 1, ks->probe.p + 1, 1, ks->cs));
   double bad = 1.0;
-  KS_HIP(hipMemcpyAsync(&bad, ks->probe.p + 1, sizeof(double), hipMemcpyDeviceToHost, ks->cs));
-  KS_HIP(hipStreamSynchronize(ks->cs));
+  HIPCHK(hipMemcpyAsync(&bad, ks->probe.p + 1, sizeof(double), hipMemcpyDeviceToHost, ks->cs));
+  HIPCHK(hipStreamSynchronize(ks->cs));
   *ok = bad == 0.0 ? 1 : 0;
   ks->rs_premul.emplace_back(count, *ok);
   return QCE_OK;
@@ -612,8 +572,8 @@ int reduce_chunks(qce_kshard* ks, const std::vector<Chunk>& L, bool scatter, int
   const int N = ks->m->N;  // every table set has the same N
   const Chunk& ch = L[chunk_index];
   hipEvent_t ev = ks->ev_chunk[chunk_index];
-  KS_HIP(hipEventRecord(ev, st));
-  KS_HIP(hipStreamWaitEvent(ks->cs, ev, 0));
+  HIPCHK(hipEventRecord(ev, st));
+  HIPCHK(hipStreamWaitEvent(ks->cs, ev, 0));
   double* send = ks->pkb[ks->pkp].p + ch.pk_off * W;
   const double* rows;
   if (scatter) {
@@ -636,7 +596,7 @@ int reduce_chunks(qce_kshard* ks, const std::vector<Chunk>& L, bool scatter, int
       if (!ok || !rs_premul_allowed()) {
         hipLaunchKernelGGL(k_ks_scale_rows, dim3(rowpass_grid(ch.npad * W)), dim3(256), 0, ks->cs, ch.npad * W, send,
                            premul);
-        KS_HIP(hipGetLastError());
+        HIPCHK(hipGetLastError());
         premul = nullptr;
       }
     }
@@ -650,7 +610,7 @@ int reduce_chunks(qce_kshard* ks, const std::vector<Chunk>& L, bool scatter, int
   if (ch.nv > 0) {
     hipLaunchKernelGGL(k_ks_finalize, dim3(rowpass_grid(ch.nv * N)), dim3(256), 0, ks->cs, ch.nv, N, rows,
                        h_out + ch.h_off * N, count_flags ? kUnderflowS : -1.0, ks->cnt.p);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   return QCE_OK;
 }
@@ -658,7 +618,7 @@ int reduce_chunks(qce_kshard* ks, const std::vector<Chunk>& L, bool scatter, int
 int ensure_events(qce_kshard* ks, size_t n) {
   while (ks->ev_chunk.size() < n) {
     hipEvent_t e;
-    KS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     ks->ev_chunk.push_back(e);
   }
   return QCE_OK;
@@ -668,13 +628,13 @@ int ensure_events(qce_kshard* ks, size_t n) {
 int close_step(qce_kshard* ks) {
   hipLaunchKernelGGL(k_ks_flags, dim3(1), dim3(64), 0, ks->cs, ks->cnt.p, ks->step_shift.p + 2 * ks->pkp + 1,
                      ks->local_chol, ks->fl.p);
-  KS_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   KS_RC(collective(ks->c, QCE_COLL_ALLREDUCE_MAX, ks->fl.p, ks->fl.p, 2, ks->cs));
-  KS_HIP(hipMemcpyAsync(ks->host_fl, ks->fl.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ks->cs));
-  KS_HIP(hipMemcpyAsync(ks->host_fl + 2, ks->earlier.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ks->cs));
-  KS_HIP(hipEventRecord(ks->ev_done, ks->cs));  // h_out complete (the caller's stream waits for it in finish)
+  HIPCHK(hipMemcpyAsync(ks->host_fl, ks->fl.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ks->cs));
+  HIPCHK(hipMemcpyAsync(ks->host_fl + 2, ks->earlier.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ks->cs));
+  HIPCHK(hipEventRecord(ks->ev_done, ks->cs));  // h_out complete (the caller's stream waits for it in finish)
   // the last reader of this parity's send rows and shift slots: step t+2 (the next user of the parity) waits for it
-  KS_HIP(hipEventRecord(ks->ev_pk[ks->pkp], ks->cs));
+  HIPCHK(hipEventRecord(ks->ev_pk[ks->pkp], ks->cs));
   ks->pk_valid[ks->pkp] = 1;
   return QCE_OK;
 }
@@ -683,14 +643,14 @@ int close_step(qce_kshard* ks) {
 // stream hand-offs: every data collective is issued on the communication stream (one stream per communicator)
 int st_to_cs(qce_kshard* ks, hipStream_t st) {
   if (st == ks->cs) return QCE_OK;
-  KS_HIP(hipEventRecord(ks->ev_st2cs, st));
-  KS_HIP(hipStreamWaitEvent(ks->cs, ks->ev_st2cs, 0));
+  HIPCHK(hipEventRecord(ks->ev_st2cs, st));
+  HIPCHK(hipStreamWaitEvent(ks->cs, ks->ev_st2cs, 0));
   return QCE_OK;
 }
 int cs_to_st(qce_kshard* ks, hipStream_t st) {
   if (st == ks->cs) return QCE_OK;
-  KS_HIP(hipEventRecord(ks->ev_cs2st, ks->cs));
-  KS_HIP(hipStreamWaitEvent(st, ks->ev_cs2st, 0));
+  HIPCHK(hipEventRecord(ks->ev_cs2st, ks->cs));
+  HIPCHK(hipStreamWaitEvent(st, ks->ev_cs2st, 0));
   return QCE_OK;
 }
 
@@ -702,15 +662,15 @@ int agree_shift(qce_kshard* ks, hipStream_t st) {
   double* sh = ks->step_shift.p + 2 * ks->pkp;
   KS_RC(st_to_cs(ks, st));
   hipLaunchKernelGGL(k_ks_shift_in, dim3(1), dim3(64), 0, ks->cs, ks->shift.p + ks->cur, sh);
-  KS_HIP(hipGetLastError());
-  KS_HIP(hipEventRecord(ks->ev_shift_read, ks->cs));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ks->ev_shift_read, ks->cs));
   ks->shift_read_valid = 1;
-  if (ks->mods[1]) KS_HIP(hipEventRecord(ks->ev_shift_rd[ks->cur], ks->cs));
+  if (ks->mods[1]) HIPCHK(hipEventRecord(ks->ev_shift_rd[ks->cur], ks->cs));
   KS_RC(collective(ks->c, QCE_COLL_ALLREDUCE_MAX, sh + 1, sh + 1, 1, ks->cs));
   double bias = 0.0;
   if (const char* b = getenv("QCE_KSHARD_GLOBAL_BIAS")) bias = atof(b);  // tests only
   hipLaunchKernelGGL(k_ks_scale_of, dim3(1), dim3(64), 0, ks->cs, sh, bias, ks->scale.p + ks->pkp);
-  KS_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return QCE_OK;
 }
 
@@ -726,9 +686,9 @@ int step_all(qce_kshard* ks, qce_model* m, const double2* y, long long B, int ch
     pk_rows += ch.npad;
     if (scatter) rs_rows += ch.npad / ks->lw;
   }
-  KBuf<double>& pkbuf = ks->pkb[ks->pkp];
-  KS_HIP(pkbuf.ensure((size_t)pk_rows * W));
-  if (scatter) KS_HIP(ks->rs.ensure((size_t)rs_rows * W));
+  DevBuf<double>& pkbuf = ks->pkb[ks->pkp];
+  HIPCHK(pkbuf.ensure((size_t)pk_rows * W));
+  if (scatter) HIPCHK(ks->rs.ensure((size_t)rs_rows * W));
   KS_RC(ensure_events(ks, L.size()));
   if (scatter && !rowshift && !ks->agree_first && c->kind == QCE_COMM_RCCL && rs_premul_allowed()) {
     for (const Chunk& ch : L) {  // each new count checked once, in the rows this step is about to fill
@@ -741,16 +701,16 @@ int step_all(qce_kshard* ks, qce_model* m, const double2* y, long long B, int ch
   int hard = QCE_OK;
   if (rowshift) {
     // exact recombination: m (running max), s, acc of this shard for the whole batch; mg = MAX over shards of m
-    KS_HIP(ks->rm.ensure((size_t)B));
-    KS_HIP(ks->rsum.ensure((size_t)B));
-    KS_HIP(ks->racc.ensure((size_t)B * 2 * N));
-    KS_HIP(ks->mg.ensure((size_t)B));
+    HIPCHK(ks->rm.ensure((size_t)B));
+    HIPCHK(ks->rsum.ensure((size_t)B));
+    HIPCHK(ks->racc.ensure((size_t)B * 2 * N));
+    HIPCHK(ks->mg.ensure((size_t)B));
     if (!guarded(ks, qce_estimate_partial_f64(m, reinterpret_cast<const double*>(y), B, ks->rm.p, ks->rsum.p,
                                               ks->racc.p, QCE_IO_DEVICE, st), &hard)) {
       if (hard) return hard;
-      KS_HIP(hipMemsetAsync(ks->rm.p, 0xff, sizeof(double) * B, st));  // NaN rows; the Cholesky flag raises first
+      HIPCHK(hipMemsetAsync(ks->rm.p, 0xff, sizeof(double) * B, st));  // NaN rows; the Cholesky flag raises first
     }
-    KS_HIP(hipMemcpyAsync(ks->mg.p, ks->rm.p, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(ks->mg.p, ks->rm.p, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
     KS_RC(st_to_cs(ks, st));
     KS_RC(collective(c, QCE_COLL_ALLREDUCE_MAX, ks->mg.p, ks->mg.p, B, ks->cs));
     KS_RC(cs_to_st(ks, st));
@@ -759,11 +719,11 @@ int step_all(qce_kshard* ks, qce_model* m, const double2* y, long long B, int ch
     const Chunk& ch = L[i];
     const long long n = ch.hi - ch.lo;
     double* pk = pkbuf.p + ch.pk_off * W;
-    if (ch.npad > n) KS_HIP(hipMemsetAsync(pk + n * W, 0, sizeof(double) * (ch.npad - n) * W, st));
+    if (ch.npad > n) HIPCHK(hipMemsetAsync(pk + n * W, 0, sizeof(double) * (ch.npad - n) * W, st));
     if (rowshift) {
       hipLaunchKernelGGL(k_ks_pack_rowshift, dim3(grid_for(n * W)), dim3(256), 0, st, n, N, ks->rm.p + ch.lo,
                          ks->rsum.p + ch.lo, ks->racc.p + ch.lo * 2 * N, ks->mg.p + ch.lo, pk);
-      KS_HIP(hipGetLastError());
+      HIPCHK(hipGetLastError());
     } else {
       bool ok = false;
       if (!ks->local_chol) {
@@ -777,7 +737,7 @@ int step_all(qce_kshard* ks, qce_model* m, const double2* y, long long B, int ch
         if (hard) return hard;
         KS_RC(timed_end(ks, st));
       }
-      if (!ok) KS_HIP(hipMemsetAsync(pk, 0, sizeof(double) * n * W, st));
+      if (!ok) HIPCHK(hipMemsetAsync(pk, 0, sizeof(double) * n * W, st));
     }
     KS_RC(reduce_chunks(ks, L, scatter, W, st, h, !rowshift, i,
                         (rowshift || ks->agree_first) ? nullptr : ks->scale.p + ks->pkp));
@@ -811,11 +771,11 @@ int step_select(qce_kshard* ks, const double2* y, long long B, int mode, double 
   std::vector<Chunk> L = chunk_layout(B, 1, c->world, c->rank, scatter);
   KS_RC(ensure_events(ks, 1));
   const long long npad = L[0].npad;
-  KS_HIP(ks->lp.ensure((size_t)B * Kl));
-  KS_HIP(ks->wloc.ensure((size_t)B * Kl));
-  KBuf<double>& pkbuf = ks->pkb[ks->pkp];
-  KS_HIP(pkbuf.ensure((size_t)npad * W));
-  if (scatter) KS_HIP(ks->rs.ensure((size_t)(npad / c->world) * W));
+  HIPCHK(ks->lp.ensure((size_t)B * Kl));
+  HIPCHK(ks->wloc.ensure((size_t)B * Kl));
+  DevBuf<double>& pkbuf = ks->pkb[ks->pkp];
+  HIPCHK(pkbuf.ensure((size_t)npad * W));
+  if (scatter) HIPCHK(ks->rs.ensure((size_t)(npad / c->world) * W));
   int hard = QCE_OK;
   bool ok = false;
   if (!ks->local_chol) {
@@ -825,57 +785,57 @@ int step_select(qce_kshard* ks, const double2* y, long long B, int mode, double 
     if (hard) return hard;
     KS_RC(timed_end(ks, st));
   }
-  if (!ok) KS_HIP(hipMemsetAsync(ks->lp.p, 0, sizeof(double) * B * Kl, st));
+  if (!ok) HIPCHK(hipMemsetAsync(ks->lp.p, 0, sizeof(double) * B * Kl, st));
   if (kmode == 3) {
     // argmax: (max lp, local index) per row and shard -> the owner of the first global maximum
-    KS_HIP(ks->lpad.ensure((size_t)B * 2));
-    KS_HIP(ks->gath.ensure((size_t)B * 2 * c->world));
+    HIPCHK(ks->lpad.ensure((size_t)B * 2));
+    HIPCHK(ks->gath.ensure((size_t)B * 2 * c->world));
     hipLaunchKernelGGL(k_ks_row_argmax, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, B, Kl, ks->lp.p, ks->lpad.p);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     KS_RC(st_to_cs(ks, st));
     KS_RC(collective(c, QCE_COLL_ALLGATHER, ks->lpad.p, ks->gath.p, B * 2, ks->cs));
     KS_RC(cs_to_st(ks, st));
     hipLaunchKernelGGL(k_ks_argmax_weights, dim3(grid_for(B)), dim3(256), 0, st, B, c->world, c->rank, Kl,
                        ks->gath.p, ks->wloc.p);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   } else {
     const int K = ks->K, Kmax = ks->Kmax;
-    KS_HIP(ks->lpad.ensure((size_t)B * Kmax));
-    KS_HIP(ks->gath.ensure((size_t)B * Kmax * c->world));
-    KS_HIP(ks->lpfull.ensure((size_t)B * K));
-    KS_HIP(ks->wfull.ensure((size_t)B * K));
+    HIPCHK(ks->lpad.ensure((size_t)B * Kmax));
+    HIPCHK(ks->gath.ensure((size_t)B * Kmax * c->world));
+    HIPCHK(ks->lpfull.ensure((size_t)B * K));
+    HIPCHK(ks->wfull.ensure((size_t)B * K));
     hipLaunchKernelGGL(k_ks_pad, dim3(grid_for(B * Kmax)), dim3(256), 0, st, B, Kl, Kmax, ks->lp.p, ks->lpad.p);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     KS_RC(st_to_cs(ks, st));
     KS_RC(collective(c, QCE_COLL_ALLGATHER, ks->lpad.p, ks->gath.p, B * Kmax, ks->cs));
     KS_RC(cs_to_st(ks, st));
     hipLaunchKernelGGL(k_ks_assemble, dim3(grid_for(B * K)), dim3(256), 0, st, B, c->world, K, Kmax, ks->gath.p,
                        ks->lpfull.p);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     // the same FP64 selection on every rank (gmm_cplx_bussgang.py:213, :235-236)
-    KS_HIP(qce_launch_select(B, K, ks->lpfull.p, kmode, nsel, p, nullptr, nullptr, nullptr, st, ks->wfull.p));
+    HIPCHK(qce_launch_select(B, K, ks->lpfull.p, kmode, nsel, p, nullptr, nullptr, nullptr, st, ks->wfull.p));
     hipLaunchKernelGGL(k_ks_slice, dim3(grid_for(B * Kl)), dim3(256), 0, st, B, K, ks->lo, Kl, ks->wfull.p,
                        ks->wloc.p);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   // this shard's share of sum_k w_bk (W_k y_b + b_k), written straight into the collective's rows (a row of 2N
   // doubles is one c128 row of h)
-  if (npad > B) KS_HIP(hipMemsetAsync(pkbuf.p + B * W, 0, sizeof(double) * (npad - B) * W, st));
+  if (npad > B) HIPCHK(hipMemsetAsync(pkbuf.p + B * W, 0, sizeof(double) * (npad - B) * W, st));
   ok = false;
   if (!ks->local_chol) {
     ok = guarded(ks, qce_weighted_estimate(m, y, B, ks->wloc.p, reinterpret_cast<double2*>(pkbuf.p), st), &hard);
     if (hard) return hard;
   }
-  if (!ok) KS_HIP(hipMemsetAsync(pkbuf.p, 0, sizeof(double) * B * W, st));
+  if (!ok) HIPCHK(hipMemsetAsync(pkbuf.p, 0, sizeof(double) * B * W, st));
   // SUM over shards on the communication stream, rows straight into h_out
   const Chunk& ch = L[0];
-  KS_HIP(hipEventRecord(ks->ev_chunk[0], st));
-  KS_HIP(hipStreamWaitEvent(ks->cs, ks->ev_chunk[0], 0));
+  HIPCHK(hipEventRecord(ks->ev_chunk[0], st));
+  HIPCHK(hipStreamWaitEvent(ks->cs, ks->ev_chunk[0], 0));
   if (scatter) {
     const long long q = npad / c->world;
     KS_RC(collective(c, QCE_COLL_REDUCE_SCATTER_SUM, pkbuf.p, ks->rs.p, q * W, ks->cs));
     if (ch.nv > 0)
-      KS_HIP(hipMemcpyAsync(h, ks->rs.p, sizeof(double) * ch.nv * W, hipMemcpyDeviceToDevice, ks->cs));
+      HIPCHK(hipMemcpyAsync(h, ks->rs.p, sizeof(double) * ch.nv * W, hipMemcpyDeviceToDevice, ks->cs));
   } else {
     KS_RC(collective(c, QCE_COLL_ALLREDUCE_SUM, pkbuf.p, reinterpret_cast<double*>(h), B * W, ks->cs));
   }
@@ -902,7 +862,7 @@ int qce_comm_init(const void* unique_id, int rank, int world, int device, qce_co
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return qce_set_error(QCE_EARG, "device index out of range");
-  DevGuard g(device);
+  DeviceGuard g(device);
   ncclUniqueId id;
   memcpy(&id, unique_id, sizeof(id));
   qce_comm* c = new qce_comm();
@@ -936,7 +896,7 @@ int qce_comm_init_host(int rank, int world, int device, qce_host_collective fn, 
 
 int qce_comm_destroy(qce_comm* c) {
   if (!c) return QCE_OK;
-  DevGuard g(c->device);
+  DeviceGuard g(c->device);
   if (c->nc) (void)ncclCommDestroy(c->nc);
   if (c->pin_send) (void)hipHostFree(c->pin_send);
   if (c->pin_recv) (void)hipHostFree(c->pin_recv);
@@ -958,6 +918,14 @@ int qce_kshard_slice(int K, int world, int rank, int* lo, int* hi) {
   if (world < 1 || rank < 0 || rank >= world || K < world)
     return qce_set_error(QCE_EARG, "K-shard split needs K >= world and 0 <= rank < world");
   slice_of(K, world, rank, lo, hi);
+  return QCE_OK;
+}
+
+int qce_kshard_layout(int world, int rank, int* layout_world, int* layout_rank) {
+  if (!layout_world || !layout_rank) return qce_set_error(QCE_EARG, "null argument");
+  *layout_world = world;
+  *layout_rank = rank;
+  if (world == 1) (void)kshard_emulated(layout_world, layout_rank);
   return QCE_OK;
 }
 
@@ -985,11 +953,9 @@ int qce_kshard_create(qce_model* shard, qce_comm* comm, int K_total, qce_kshard*
   if (hi - lo != shard->K)
     return qce_set_error(QCE_EARG, "the shard model must hold components [" + std::to_string(lo) + ", " +
                                        std::to_string(hi) + ") of the balanced split (qce_kshard_slice)");
-  DevGuard g(shard->device);
+  DeviceGuard g(shard->device);
   qce_kshard* ks = new qce_kshard();
-  ks->lw = comm->world;
-  ks->lr = comm->rank;
-  if (comm->world == 1) (void)kshard_emulated(&ks->lw, &ks->lr);
+  (void)qce_kshard_layout(comm->world, comm->rank, &ks->lw, &ks->lr);
   if (comm->kind == QCE_COMM_RCCL && ks->lw > 1) ks->reserve = kshard_reserve_cus();
   if (const char* af = getenv("QCE_KSHARD_AGREE_FIRST")) {
     ks->agree_first = atoi(af);
@@ -1029,13 +995,8 @@ int qce_kshard_create(qce_model* shard, qce_comm* comm, int K_total, qce_kshard*
 
 int qce_kshard_destroy(qce_kshard* ks) {
   if (!ks) return QCE_OK;
-  DevGuard g(ks->device);
+  DeviceGuard g(ks->device);
   if (ks->cs) (void)hipStreamSynchronize(ks->cs);
-  for (auto* b : {&ks->shift, &ks->fl, &ks->earlier, &ks->pkb[0], &ks->pkb[1], &ks->step_shift, &ks->scale, &ks->probe, &ks->rs,
-                  &ks->rm, &ks->rsum, &ks->racc, &ks->mg, &ks->lp, &ks->lpad, &ks->gath, &ks->lpfull, &ks->wfull,
-                  &ks->wloc})
-    b->release();
-  ks->cnt.release();
   for (hipEvent_t e : ks->ev_chunk) (void)hipEventDestroy(e);
   for (auto& pr : ks->tev) {
     (void)hipEventDestroy(pr.first);
@@ -1057,14 +1018,14 @@ int qce_kshard_destroy(qce_kshard* ks) {
   }
   if (ks->host_fl) (void)hipHostFree(ks->host_fl);
   if (ks->cs) (void)hipStreamDestroy(ks->cs);
-  delete ks;
+  delete ks;  // every DevBuf frees its memory here, still under the device guard
   return QCE_OK;
 }
 
 int qce_kshard_prepare(qce_kshard* ks, const double* A, int M, double snr_db, double n_bits, int quant_kind,
                        const double* thresholds, const double* labels, int n_levels, void* stream) {
   if (!ks) return qce_set_error(QCE_EARG, "null K-shard");
-  DevGuard g(ks->device);
+  DeviceGuard g(ks->device);
   hipStream_t st = ks_stream(ks, stream);
   const bool dbl = ks->mods[1] != nullptr;
   // with a spare table set the prepare fills the set the previous step did NOT read, on the prepare stream, so it
@@ -1073,12 +1034,12 @@ int qce_kshard_prepare(qce_kshard* ks, const double* A, int M, double snr_db, do
   qce_model* m = ks->mods[j];
   hipStream_t ps = dbl ? ks->ps : st;
   if (dbl && ks->used_valid[j]) {
-    KS_HIP(hipStreamWaitEvent(ps, ks->ev_used[j], 0));
-    KS_HIP(hipStreamWaitEvent(ps, ks->ev_shift_rd[j], 0));
+    HIPCHK(hipStreamWaitEvent(ps, ks->ev_used[j], 0));
+    HIPCHK(hipStreamWaitEvent(ps, ks->ev_shift_rd[j], 0));
   }
   // one table set: its shift slot is read on the communication stream at the start of each step (agree_shift), which
   // may lag behind the compute stream; the prepare that rewrites it waits for that read
-  if (!dbl && ks->shift_read_valid) KS_HIP(hipStreamWaitEvent(ps, ks->ev_shift_read, 0));
+  if (!dbl && ks->shift_read_valid) HIPCHK(hipStreamWaitEvent(ps, ks->ev_shift_read, 0));
   if (ks->pending.valid && ks->pending.model == m) ks->pending.stale = 1;  // its tables are being replaced
   ks->cur = j;
   ks->m = m;
@@ -1089,16 +1050,16 @@ int qce_kshard_prepare(qce_kshard* ks, const double* A, int M, double snr_db, do
   if (!guarded(ks, qce_cconst_max(m, shift, QCE_IO_DEVICE, ps), &hard)) {
     if (hard) return hard;
     const double inf = __builtin_inf();  // the failure rides the shift as the kernel would have written it
-    KS_HIP(hipMemcpyAsync(shift, &inf, sizeof(double), hipMemcpyHostToDevice, ps));
-    KS_HIP(hipStreamSynchronize(ps));
+    HIPCHK(hipMemcpyAsync(shift, &inf, sizeof(double), hipMemcpyHostToDevice, ps));
+    HIPCHK(hipStreamSynchronize(ps));
   }
   // no collective here: the shards agree on M* at the start of the step that uses these tables (agree_shift), on the
   // communication stream behind the previous step's collectives, so every rank issues its collectives in one order
   if (const char* b = getenv("QCE_KSHARD_SHIFT_BIAS")) {  // tests only: force the underflow path
     hipLaunchKernelGGL(k_ks_add, dim3(1), dim3(64), 0, ps, shift, atof(b));
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  if (dbl) KS_HIP(hipEventRecord(ks->ev_prep[j], ps));
+  if (dbl) HIPCHK(hipEventRecord(ks->ev_prep[j], ps));
   return QCE_OK;
 }
 
@@ -1107,12 +1068,12 @@ int qce_kshard_set_spare(qce_kshard* ks, qce_model* spare) {
   const qce_model* a = ks->mods[0];
   if (spare == a || spare->K != a->K || spare->N != a->N || spare->device != a->device)
     return qce_set_error(QCE_EARG, "the spare model must be a second model of the same shard (same K, N, device)");
-  DevGuard g(ks->device);
-  KS_HIP(hipStreamCreateWithFlags(&ks->ps, hipStreamNonBlocking));
+  DeviceGuard g(ks->device);
+  HIPCHK(hipStreamCreateWithFlags(&ks->ps, hipStreamNonBlocking));
   for (int i = 0; i < 2; ++i) {
-    KS_HIP(hipEventCreateWithFlags(&ks->ev_prep[i], hipEventDisableTiming));
-    KS_HIP(hipEventCreateWithFlags(&ks->ev_used[i], hipEventDisableTiming));
-    KS_HIP(hipEventCreateWithFlags(&ks->ev_shift_rd[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ks->ev_prep[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ks->ev_used[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ks->ev_shift_rd[i], hipEventDisableTiming));
   }
   ks->mods[1] = spare;
   return QCE_OK;
@@ -1123,29 +1084,29 @@ int qce_kshard_estimate(qce_kshard* ks, const double* y, int64_t B, int mode, do
   if (!ks) return qce_set_error(QCE_EARG, "null K-shard");
   if (B < 0 || (B > 0 && (!y || !h_out))) return qce_set_error(QCE_EARG, "bad y / h_out");
   if (!ks->m->prepared && !ks->local_chol) return qce_set_error(QCE_ESTATE, "qce_kshard_prepare has not been called");
-  DevGuard g(ks->device);
+  DeviceGuard g(ks->device);
   hipStream_t st = ks_stream(ks, stream);
   // a step superseded before finish(): its flags fold into the running `earlier` word
   if (ks->pending.valid) {
     hipLaunchKernelGGL(k_ks_fold, dim3(1), dim3(64), 0, ks->cs, ks->earlier.p, ks->fl.p);
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     ks->any_pending_before = 1;
   }
-  KS_HIP(hipMemsetAsync(ks->cnt.p, 0, sizeof(unsigned), ks->cs));
+  HIPCHK(hipMemsetAsync(ks->cnt.p, 0, sizeof(unsigned), ks->cs));
   const double2* yd = reinterpret_cast<const double2*>(y);
   double2* hd = reinterpret_cast<double2*>(h_out);
   const bool dbl = ks->mods[1] != nullptr;
-  if (dbl) KS_HIP(hipStreamWaitEvent(st, ks->ev_prep[ks->cur], 0));
+  if (dbl) HIPCHK(hipStreamWaitEvent(st, ks->ev_prep[ks->cur], 0));
   // this step's send rows: the buffer the previous step's collectives do not read, once the step before that (the
   // last reader of this parity, still in flight on the comm stream) is done with it; the shard's shift, kept in the
   // parity's slot (the next prepare may overwrite the table set's slot before the comm stream gets there)
   ks->pkp ^= 1;
-  if (ks->pk_valid[ks->pkp]) KS_HIP(hipStreamWaitEvent(st, ks->ev_pk[ks->pkp], 0));
+  if (ks->pk_valid[ks->pkp]) HIPCHK(hipStreamWaitEvent(st, ks->ev_pk[ks->pkp], 0));
   if (const char* d = getenv("QCE_KSHARD_CS_DELAY_US")) {  // tests only
     int rate_khz = 0;
-    KS_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, ks->device));
+    HIPCHK(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, ks->device));
     hipLaunchKernelGGL(k_ks_spin, dim3(1), dim3(64), 0, ks->cs, (long long)(atof(d) * rate_khz / 1000.0));
-    KS_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   KS_RC(agree_shift(ks, st));
   if (ks->agree_first == 1 && mode == QCE_MODE_ALL && B > 0) KS_RC(cs_to_st(ks, st));  // the partial reads M*
@@ -1161,7 +1122,7 @@ int qce_kshard_estimate(qce_kshard* ks, const double* y, int64_t B, int mode, do
   // (round 5 waited for the step's close on cs; emulated world-8 rank step 1.107 / 1.103 -> 1.080 / 1.097 ms,
   // profiles/r06_kshard_prepare_order_ab.jsonl)
   if (dbl) {
-    KS_HIP(hipEventRecord(ks->ev_used[ks->cur], st));
+    HIPCHK(hipEventRecord(ks->ev_used[ks->cur], st));
     ks->used_valid[ks->cur] = 1;
   }
   KS_RC(st_to_cs(ks, st));  // the flag word closes the step behind its last kernel
@@ -1181,15 +1142,15 @@ int qce_kshard_estimate(qce_kshard* ks, const double* y, int64_t B, int mode, do
 int qce_kshard_finish(qce_kshard* ks, void* stream) {
   if (!ks) return qce_set_error(QCE_EARG, "null K-shard");
   if (!ks->pending.valid) return QCE_OK;
-  DevGuard g(ks->device);
+  DeviceGuard g(ks->device);
   hipStream_t st = ks_stream(ks, stream);
-  KS_HIP(hipEventSynchronize(ks->ev_done));
+  HIPCHK(hipEventSynchronize(ks->ev_done));
   const double f0 = ks->host_fl[0], f1 = ks->host_fl[1], e0 = ks->host_fl[2], e1 = ks->host_fl[3];
   for (int i = 0; i < 4; ++i) ks->last_flags[i] = ks->host_fl[i];
   auto pend = ks->pending;
   ks->pending.valid = 0;
   ks->any_pending_before = 0;
-  KS_HIP(hipMemsetAsync(ks->earlier.p, 0, 2 * sizeof(double), ks->cs));
+  HIPCHK(hipMemsetAsync(ks->earlier.p, 0, 2 * sizeof(double), ks->cs));
   if (f1 > 0.0 || e1 > 0.0) return qce_set_error(QCE_ECHOL, kCholMessage);
   if (e0 > 0.0)
     return qce_set_error(QCE_ESTATE, "an earlier K-shard estimate had rows whose shifted sum underflowed; call "
@@ -1201,10 +1162,10 @@ int qce_kshard_finish(qce_kshard* ks, void* stream) {
     // exact recombination of the last step (every rank agrees through the MAX of the flag word), all of it on the
     // communication stream (its collectives are data-communicator work)
     KS_RC(step_all(ks, pend.model, pend.y, pend.B, pend.chunks, pend.scatter != 0, pend.h, ks->cs, true));
-    KS_HIP(hipEventRecord(ks->ev_done, ks->cs));
-    KS_HIP(hipEventSynchronize(ks->ev_done));
+    HIPCHK(hipEventRecord(ks->ev_done, ks->cs));
+    HIPCHK(hipEventSynchronize(ks->ev_done));
   }
-  KS_HIP(hipStreamWaitEvent(st, ks->ev_done, 0));  // the caller's stream sees h complete
+  HIPCHK(hipStreamWaitEvent(st, ks->ev_done, 0));  // the caller's stream sees h complete
   return QCE_OK;
 }
 
@@ -1223,12 +1184,12 @@ int qce_kshard_timing(qce_kshard* ks, int enable) {
 
 int qce_kshard_kernel_ms(qce_kshard* ks, double* total_ms, int* launches) {
   if (!ks || !total_ms) return qce_set_error(QCE_EARG, "null argument");
-  DevGuard g(ks->device);
+  DeviceGuard g(ks->device);
   double t = 0.0;
   for (size_t i = 0; i < ks->tev_used; ++i) {
-    KS_HIP(hipEventSynchronize(ks->tev[i].second));
+    HIPCHK(hipEventSynchronize(ks->tev[i].second));
     float ms = 0.0f;
-    KS_HIP(hipEventElapsedTime(&ms, ks->tev[i].first, ks->tev[i].second));
+    HIPCHK(hipEventElapsedTime(&ms, ks->tev[i].first, ks->tev[i].second));
     t += ms;
   }
   *total_ms = t;

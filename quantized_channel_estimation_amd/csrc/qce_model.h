@@ -1,5 +1,5 @@
 // Private layout of a qce_model (the opaque handle of include/qce.h), shared by the C-ABI units
-// (qce_capi.hip: model lifetime / prepare / estimate; qce_kshard.hip: the K-shard step over a communicator).
+// (qce_capi*.hip: model lifetime / prepare / estimate; qce_kshard.hip: the K-shard step over a communicator).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,10 +8,17 @@
 
 #include "qce_kernels.h"
 
+// A device buffer that owns its memory.  Only ever a member of a handle (qce_model, qce_kshard) that an explicit
+// destroy call deletes under the device guard while the HIP runtime is up: never static or thread-local, so no
+// hipFree runs at process exit.
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t count) {
     if (count <= n && p) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -26,6 +33,19 @@ struct DevBuf {
     p = nullptr;
     n = 0;
   }
+};
+
+// The kernel family that serves 'all' / partial / log-prob calls of a prepared model.  Chosen in one place
+// (select_backend, qce_capi_prepare.hip) and switched on by every entry point.
+enum QceBackend {
+  QCE_BE_NONE = 0,     // not prepared
+  QCE_BE_FOURIER,      // (block-)circulant mixture, Fourier-domain tables (qce_fft.hip / qce_fft_mfma.hip)
+  QCE_BE_BIG,          // N or M beyond 256: GEMM-based FP64 path (qce_big.hip)
+  QCE_BE_F64_4M,       // fused FP64 kernel k_est_all_f64
+  QCE_BE_F64_3M,       // 3M layout, padded <= 64 (k_est_all_f64g)
+  QCE_BE_F64_3M_128,   // 3M layout at padded 128 (k_est_all_f64h)
+  QCE_BE_F64_WIDE,     // beyond padded 128: the two-pass FP64 path (qce_wsum_f64.hip)
+  QCE_BE_FAST,         // fp16-split / FP32-MFMA kernels (QCE_KERNEL picks between them per launch)
 };
 
 struct qce_model {
@@ -46,6 +66,9 @@ struct qce_model {
   DevBuf<double> logw;
   // prepared state
   int M = 0, MP = 0, NP = 0, prepared = 0;
+  // Family of the last prepare.  A Fourier prepare leaves the dense tables (and MP / NP) of an earlier prepare
+  // behind; dense_valid says whether they match this prepare (ensure_dense replays it without touching `backend`).
+  QceBackend backend = QCE_BE_NONE;
   DevBuf<double2> A, Cy, Cr, Lw, Linv, Aeff, work, V, W, means_y, q0, bvec;
   DevBuf<double> gain, cconst, thr, lab;
   DevBuf<int> status;
@@ -70,10 +93,7 @@ struct qce_model {
   DevBuf<int> yflag;
   // FP64 fused-kernel tables (qce_estimate_f64.hip) and its cut-tile scratch
   DevBuf<char> pack_f64;
-  int f64_g3 = 0;  // pack_f64 holds the 3M layout (k_est_all_f64g)
-  int f64_active = 0;  // the last dense prepare packed FP64 tables: 'all' / partial run k_est_all_f64
-  DevBuf<char> pack_ws;
-  int f64_wide = 0;    // ... or, beyond padded 128, the two-pass FP64 path (qce_wsum_f64.hip)
+  DevBuf<char> pack_ws;  // ... and of the two-pass path (qce_wsum_f64.hip)
   int pack64_valid = 0;  // pack64 (the k_lp_f64 table) built without pack32
   DevBuf<double> fp_m, fp_s, fp_a;
   DevBuf<double> part_a64;  // FP64 partial accumulator behind the f32 qce_estimate_partial
@@ -87,13 +107,11 @@ struct qce_model {
   int reserve_set = 0;  // the caller set QCE_OPT_RESERVE_CUS (a K-shard step then keeps the caller's value)
   int sched_cus() const { return cu_count - reserve_cus > 8 ? cu_count - reserve_cus : 8; }
   // dimensions beyond the fused kernels' 256 (qce_big.hip): GEMM-based FP64 path
-  int big = 0;
   DevBuf<double2> big_ws, big_d;  // stacked transposed filters (N x K x M); per-chunk intermediate
   int big_ws_valid = 0;
   // Fourier-domain path for (block-)circulant mixtures (qce_fft.hip): structure found at creation
   int fft_n1 = 0, fft_n2 = 0;
-  int fft_active = 0;   // the last prepare took the Fourier path (dense tables computed lazily)
-  int dense_valid = 0;  // dense tables match the last prepare
+  int dense_valid = 0;  // dense tables match the last prepare (after a Fourier prepare: computed lazily)
   DevBuf<double> f_ceig, f_rinvT, f_cprime, f_wT, f_gain;
   DevBuf<double2> f_col0, f_mspec, f_uT, f_bT;
   DevBuf<int> f_bad;
@@ -116,8 +134,7 @@ struct qce_model {
   } last;
 };
 
-// Internal entry points of qce_capi.hip used by qce_kshard.hip (C++ linkage: not part of the ABI).
-int qce_set_error(int code, const std::string& msg);  // sets qce_last_error() and returns code
+// Internal entry point of qce_capi_estimate.hip used by qce_kshard.hip (C++ linkage: not part of the ABI).
 // h_b = sum_k w[b][k] (W_k y_b + b_k), w (B x K) FP64 selection weights on the device (dense or Fourier path)
 int qce_weighted_estimate(qce_model* m, const double2* y, long long B, const double* w, double2* h, hipStream_t st);
 

@@ -143,7 +143,7 @@ def log_prob(t, X):
 # ---- the case matrix ---------------------------------------------------------------------------------------------
 # name -> (N, A, bits, kind, mu, beta_first, K, snr, family, covs);  A: "I" | ("dense", M) | ("pilots", n);
 # covs: "full" | "circulant" | (n1, n2) block-circulant.  family: DeviceModel.KERNELS name of the 'all'-mode kernel
-# the padded shape selects (qce_capi.hip prepare_impl); the Cholesky kernel of each M is named in test_gpu_prepare.py.
+# the padded shape selects (qce_capi_prepare.hip select_backend); the Cholesky kernel of each M is named in test_gpu_prepare.py.
 def _spec(N, A, bits, kind, mu, family, beta_first=False, K=3, snr=5.0, covs="full"):
     return dict(N=N, A=A, bits=bits, kind=kind, mu=mu, beta_first=beta_first, K=K, snr=snr, family=family, covs=covs)
 

@@ -81,6 +81,6 @@ def test_kshard_layout_hook_parsing(monkeypatch):
     assert kshard_layout(2, 1) == (2, 1)  # a real multi-rank communicator keeps its layout
     monkeypatch.setenv("QCE_KSHARD_EMULATE_WORLD", "8:7")
     assert kshard_layout(1, 0) == (8, 7)
-    for bad in ("8:8", "1", "x", "4:-1"):
+    for bad in ("8:8", "1", "x", "4:-1", "8:", "8 ", "8:3 ", "1_0"):
         monkeypatch.setenv("QCE_KSHARD_EMULATE_WORLD", bad)
         assert kshard_layout(1, 0) == (1, 0), bad
