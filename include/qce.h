@@ -191,6 +191,20 @@ int qce_em_mstep(const double* X, int64_t B, int N, int K, const double* resp, d
                  int zero_mean, double* nk_out, double* means_out, double* covs_out, int device, int io,
                  void* stream);
 
+/* The two weighted statistics of `est_cov_from_quant` (cov_est_quant.py:31-88), for all K components of
+ * `estimate_gaussian_covariances_full` / `_inv` (gmm_cplx_quant.py:817, :915) in one pass over X:
+ * with d = x_b - means[k] (means (K,N) c128, NULL: d = x_b) and r = resp[b][k] (resp (B,K) f64, NULL: r = 1, K = 1),
+ * nk_out (K,) = sum_b r + 10 eps (the M-step's nk),
+ * corr_out (K,N,N) c128 = sum_b r s s^H / nk, s = (sign Re d + j sign Im d) / sqrt 2 (:27-28, :45-46; sign(0) = 0),
+ * probs_out (K,N,T,2) f64 = sum_b r 1(|Re d_i| < thresholds[t]) / nk, [..][1] the same of Im d_i (:65-69; strict).
+ * thresholds: the T positive thresholds of the quantiser, ascending (:60), host memory; T = 0: corr only
+ * (probs_out may be NULL).  1 <= N <= 256, 0 <= T <= 15 (beyond: QCE_ENOTIMPL).  X / resp / means / outputs where
+ * `io` says (model-free; `stream` NULL = the null stream of `device`); the call returns when the results are written.
+ * Deterministic: no atomics, fixed summation order. */
+int qce_quant_moments(const double* X, int64_t B, int N, int K, const double* resp, const double* means,
+                      const double* thresholds, int T, double* nk_out, double* corr_out, double* probs_out,
+                      int device, int io, void* stream);
+
 /* Set a model option (QCE_OPT_*); drops the prepared state. */
 int qce_model_set_option(qce_model* model, int option, double value);
 

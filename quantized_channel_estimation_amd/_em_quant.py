@@ -7,12 +7,13 @@ The model of the observations is a GMM with two covariance sets: ``covariances_`
 unquantised covariances, what the estimator uses) and ``covariances_quant`` (the covariances of the
 quantised data, what the E-step evaluates).  Per iteration the B-sized work runs in libqce.so: the E-step
 on ``covariances_quant`` (``qce_em_estep``), the weighted moments nk, means, Q_k = sum r (x-mu)(x-mu)^H / nk
-(``qce_em_mstep``, FP64 MFMA), and for multi-bit data two more moment passes over transformed copies of
-the observations: the 1-bit signs s = (sign Re d + j sign Im d)/sqrt 2 (Q of s: the arcsine-law
-correlation) and the threshold indicators 1(|Re d| < t) + j 1(|Im d| < t) (their weighted means: the
-per-dimension probabilities the Gauss-Newton variance fit matches) of d = x (zero-mean models: transformed
-once per fit) or d = x - mu_k (models with means: per component and M-step, as the reference's diff at :817),
-and the per-component Bussgang gains (the prepare kernels).  The per-component K x (D x D) corrections (sin
+(``qce_em_mstep``, FP64 MFMA), and for multi-bit data one more pass over the same resident observations and
+responsibilities (``qce_quant_moments`` through ``covrec.quant_moments``, all K components per call): the correlation
+of the 1-bit signs s = (sign Re d + j sign Im d)/sqrt 2 (FP64 MFMA; the arcsine law's input) and the weighted means
+of the threshold indicators 1(|Re d| < t), 1(|Im d| < t) (the per-dimension probabilities the Gauss-Newton variance
+fit matches) of d = x (zero-mean models) or d = x - mu_k (models with means, as the reference's diff at :817), formed
+in registers: no transformed copy of the data exists on the host or the device.  The per-component Bussgang gains
+come from the prepare kernels.  The per-component K x (D x D) corrections (sin
 law, eigenvalue clipping, the scalar Gauss-Newton solves, the inverse-EM Sigma update of the Toeplitz types,
 A Cy A^H with the quantised variances) run on the host in FP64 NumPy, as in the reference.
 
@@ -26,7 +27,7 @@ import warnings
 import numpy as np
 from scipy.special import erf
 
-from . import _em, _lib
+from . import _em, _lib, covrec
 from .rate import quantized_variance
 
 
@@ -212,23 +213,6 @@ class DeviceBackend:
         self.em = _em.DeviceEM(X, K, "full", reg, zero_mean, device=device)
         self.K, self.device = K, device
         self.n_bits, self.sigma2, self.quantizer, self.quant_type = n_bits, sigma2, quantizer, quant_type
-        self.es = self.ez = None
-        self.T = 0
-        self.X = X
-        if n_bits not in (1, np.inf) and quantizer is not None and quantizer[0] is not None:
-            self.thr = _positive_thresholds(quantizer[0])
-            self.T = self.thr.shape[0]
-            if zero_mean:  # d = x for every component: transform once
-                S, Z = self._transforms(X)
-                self.es = _em.DeviceEM(S, K, "full", 0.0, True, device=device)
-                self.ez = _em.DeviceEM(Z, K, "diag", 0.0, False, device=device)
-
-    def _transforms(self, D):
-        """1-bit signs of D and the threshold indicators 1(|Re D| < t) + j 1(|Im D| < t), t = the positive
-        thresholds (cov_est_quant.py:42-43, :60-63)."""
-        S = (np.sign(D.real) + 1j * np.sign(D.imag)) / np.sqrt(2)
-        Z = np.concatenate([(np.abs(D.real) < t) + 1j * (np.abs(D.imag) < t) for t in self.thr], axis=1)
-        return np.ascontiguousarray(S), np.ascontiguousarray(Z)
 
     def estep(self, means, covs_quant, weights):
         return self.em.estep(means, covs_quant, weights)
@@ -238,30 +222,10 @@ class DeviceBackend:
         return nk, means, cov
 
     def moments(self, resp=None, means=None):
-        """(corr (K, D, D), probs (K, D, T, 2)) of d = x (means None) or d = x - mu_k (per component)."""
+        """(corr (K, D, D), probs (K, D, T, 2)) of d = x (means None) or d = x - mu_k (per component): one pass
+        over the resident observations for all K components (covrec.quant_moments)."""
         R = self.em.R if resp is None else resp
-        if means is None:
-            _, _, corr = self.es.mstep(resp=R)
-            _, pz, _ = self.ez.mstep(resp=R)
-        else:
-            import torch
-            K = self.K
-            corr, pz = [], []
-            for k in range(K):
-                Rk = R[:, k:k + 1].contiguous() if isinstance(R, torch.Tensor) else np.ascontiguousarray(R[:, k:k + 1])
-                S, Z = self._transforms(self.X - means[k])
-                es = _em.DeviceEM(S, 1, "full", 0.0, True, device=self.device)
-                ez = _em.DeviceEM(Z, 1, "diag", 0.0, False, device=self.device)
-                try:
-                    corr.append(es.mstep(resp=Rk)[2][0])
-                    pz.append(ez.mstep(resp=Rk)[1][0])
-                finally:
-                    es.close()
-                    ez.close()
-            corr, pz = np.stack(corr), np.stack(pz)
-        K, D = corr.shape[0], corr.shape[1]
-        pz = pz.reshape(K, self.T, D)  # (K, T, D): real part = Re-indicator mean, imaginary = Im-indicator
-        probs = np.stack([np.real(pz), np.imag(pz)], axis=-1).transpose(0, 2, 1, 3)  # (K, D, T, 2)
+        _, corr, probs = covrec.quant_moments(self.em.X, R, means, self.quantizer[0], device=self.device)
         return corr, probs
 
     def gains(self, covs):
@@ -284,9 +248,7 @@ class DeviceBackend:
         return self.em.labels()
 
     def close(self):
-        for e in (self.em, self.es, self.ez):
-            if e is not None:
-                e.close()
+        self.em.close()
 
 
 def estimate_parameters(obj, be, resp=None, inv=False):
