@@ -172,6 +172,30 @@ int qce_observe(const double* h, int64_t B, int N, const double* A, int M, doubl
                 const double* noise, uint64_t seed, uint64_t offset, double n_bits, const double* thresholds,
                 const double* labels, int n_levels, double* y_out, int device, int io, void* stream);
 
+/* Random-SNR observations and the VAE encoder's input features (model-free): `get_observation_nbit_randSNR`
+ * and its torch variants (utils.py:254-318) with the feature step of estimators/vae.py:46-53 / :89-94, one launch:
+ *   i_b = snr_index_in[b], or drawn from {0..S-1}: cdf (S, host, cumulative probabilities) or NULL for uniform;
+ *   y_b = Q_{i_b}(A h_b + noise_scales[i_b] * w_b);  snr_index_out[b] = i_b (int32, always written).
+ * h, A, M, noise_kind, noise and n_bits as for qce_observe; noise_scales (S,) host, S <= 64.  Multi-bit: thresholds
+ * (S, n_levels - 1) and labels (S, n_levels) host arrays, one table per SNR, 2 <= n_levels <= 256.
+ * Generated draws (Philox4x32-10 keyed by seed): the noise of complex element (b, m) uses counter
+ * (row_offset + b) M + m of qce_observe's noise stream (S = 1 equals qce_observe with offset = row_offset M), the
+ * index of row b uses counter row_offset + b of a separate stream: u in [0, 1), i_b = #{cdf[i] <= u} clamped to
+ * S - 1 (uniform: floor(u S)).  Generating rows [B1, B) with row_offset = B1 reproduces the one-shot rows.
+ * out_kind: QCE_OUT_Y, out = y (B, M) c128; QCE_OUT_FEATURES_RAW / _DFT, out = float32 (B, M / N, 2 N), row (b, p) =
+ * [Re f | Im f] with f = y_b[pN:(p+1)N], or its unitary DFT (FP64 transform, rounded to float at the store); features
+ * need N in {16, 32, 64, 128, 256} and N | M, else QCE_ENOTIMPL, and a 16-byte aligned `out`.
+ * h / noise / snr_index_in / snr_index_out / out live where `io` says (host indices are range-checked, device
+ * indices are clamped to [0, S)); `stream` NULL = the null stream of `device`. */
+#define QCE_OUT_Y 0
+#define QCE_OUT_FEATURES_RAW 1
+#define QCE_OUT_FEATURES_DFT 2
+int qce_observe_randsnr(const double* h, int64_t B, int N, const double* A, int M, int S, const double* noise_scales,
+                        const double* cdf, const int32_t* snr_index_in, int32_t* snr_index_out, int noise_kind,
+                        const double* noise, uint64_t seed, uint64_t row_offset, double n_bits,
+                        const double* thresholds, const double* labels, int n_levels, int out_kind, void* out,
+                        int device, int io, void* stream);
+
 /* out[0] = sum |a_i - b_i|^2 over n complex values (the scripts' MSE numerator, Bussgang_GMM.py:289);
  * deterministic reduction order.  `out` is host memory for QCE_IO_HOST, device memory otherwise. */
 int qce_sq_error(const double* a, const double* b, int64_t n, double* out, int device, int io, void* stream);

@@ -22,6 +22,7 @@ OPT_RESERVE_CUS = 3
 PRECISION_F64, PRECISION_FAST = 0, 1
 QUANT_UNIFORM, QUANT_LLOYD, QUANT_OTHER = 0, 1, 2
 IO_HOST, IO_DEVICE = 0, 1
+OUT_Y, OUT_FEATURES_RAW, OUT_FEATURES_DFT = 0, 1, 2
 COMM_ID_BYTES = 128
 COMM_RCCL, COMM_HOST = 0, 1
 COLL_ALLREDUCE_SUM, COLL_ALLREDUCE_MAX, COLL_REDUCE_SCATTER_SUM, COLL_ALLGATHER = range(4)
@@ -80,6 +81,10 @@ SIGNATURES = {
     "qce_observe": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                    _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp,
                                    ctypes.c_int, ctypes.c_int, _vp]),
+    "qce_observe_randsnr": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                           _vp, _vp, ctypes.c_int, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.c_double, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                           ctypes.c_int, _vp]),
     "qce_sq_error": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qce_em_estep": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),
     "qce_em_mstep": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double,

@@ -103,6 +103,148 @@ int qce_observe(const double* h, int64_t B, int N, const double* A, int M, doubl
   return QCE_OK;
 }
 
+int qce_observe_randsnr(const double* h, int64_t B, int N, const double* A, int M, int S, const double* noise_scales,
+                        const double* cdf, const int32_t* snr_index_in, int32_t* snr_index_out, int noise_kind,
+                        const double* noise, uint64_t seed, uint64_t row_offset, double n_bits,
+                        const double* thresholds, const double* labels, int n_levels, int out_kind, void* out,
+                        int device, int io, void* stream) {
+  if (B < 0 || N < 1 || (A && M < 1) || (!A && M != N)) return qce_set_error(QCE_EARG, "observe_randsnr: bad shape");
+  if (S < 1 || S > QCE_ROWS_MAX_SNRS || !noise_scales)
+    return qce_set_error(QCE_EARG, "observe_randsnr: 1 to " + std::to_string(QCE_ROWS_MAX_SNRS) + " SNRs with their noise scales");
+  if (noise_kind < 0 || noise_kind > 2 || (noise_kind == 1 && !noise)) return qce_set_error(QCE_EARG, "observe_randsnr: bad noise");
+  if (io != QCE_IO_HOST && io != QCE_IO_DEVICE) return qce_set_error(QCE_EARG, "observe_randsnr: bad io");
+  if (out_kind < QCE_OUT_Y || out_kind > QCE_OUT_FEATURES_DFT) return qce_set_error(QCE_EARG, "observe_randsnr: bad output kind");
+  if (B > 0 && (!h || !out || !snr_index_out)) return qce_set_error(QCE_EARG, "observe_randsnr: null buffer");
+  if (cdf)
+    for (int i = 0; i < S; ++i)
+      if (!(cdf[i] >= (i ? cdf[i - 1] : 0.0))) return qce_set_error(QCE_EARG, "observe_randsnr: cdf must be non-decreasing from 0");
+  int kind;
+  if (n_bits == 1.0) kind = 0;
+  else if (isinf(n_bits) && n_bits > 0) kind = 2;
+  else {
+    kind = 1;
+    if (!thresholds || !labels || n_levels < 2 || n_levels > 256)
+      return qce_set_error(QCE_EARG, "observe_randsnr: multi-bit quantisation needs thresholds (S, L-1) and labels (S, L), 2 <= L <= 256");
+    for (int s = 0; s < S; ++s)
+      for (int i = 1; i < n_levels - 1; ++i)
+        if (!(thresholds[(size_t)s * (n_levels - 1) + i] >= thresholds[(size_t)s * (n_levels - 1) + i - 1]))
+          return qce_set_error(QCE_EARG, "observe_randsnr: thresholds of SNR " + std::to_string(s) + " must be increasing");
+  }
+  if (out_kind != QCE_OUT_Y) {
+    if (!qce_observe_rows_feature_shape(N))
+      return qce_set_error(QCE_ENOTIMPL, "observe_randsnr: features need n_antennas in {16, 32, 64, 128, 256}, got " + std::to_string(N));
+    if (M % N) return qce_set_error(QCE_ENOTIMPL, "observe_randsnr: features need M a multiple of n_antennas, got M = " +
+                                                      std::to_string(M) + ", N = " + std::to_string(N));
+    if (io == QCE_IO_DEVICE && ((uintptr_t)out & 15)) return qce_set_error(QCE_EARG, "observe_randsnr: feature output must be 16-byte aligned");
+  }
+  if (snr_index_in && io == QCE_IO_HOST)
+    for (int64_t b = 0; b < B; ++b)
+      if (snr_index_in[b] < 0 || snr_index_in[b] >= S) return qce_set_error(QCE_EARG, "observe_randsnr: SNR index out of range");
+  if (B == 0) return QCE_OK;
+  // A = kron(x, I_N), entry for entry: the kernel then keeps the one non-zero term of each row sum
+  int P = 0;
+  std::vector<double> xk;
+  if (A && M % N == 0) {
+    P = M / N;
+    xk.resize(2 * (size_t)P);
+    for (int p = 0; p < P; ++p) {
+      xk[2 * p] = A[2 * ((size_t)p * N * N)];
+      xk[2 * p + 1] = A[2 * ((size_t)p * N * N) + 1];
+    }
+    for (int m = 0; m < M && P; ++m)
+      for (int c = 0; c < N; ++c) {
+        const double re = A[2 * ((size_t)m * N + c)], im = A[2 * ((size_t)m * N + c) + 1];
+        const bool diag = c == m % N;
+        if (re != (diag ? xk[2 * (m / N)] : 0.0) || im != (diag ? xk[2 * (m / N) + 1] : 0.0)) {
+          P = 0;
+          break;
+        }
+      }
+  }
+  DeviceGuard g(device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t ny = (size_t)B * M, nh = (size_t)B * N;
+  const size_t out_bytes = out_kind == QCE_OUT_Y ? sizeof(double2) * ny : sizeof(float) * 2 * ny;
+  const int nthr = kind == 1 ? n_levels - 1 : 0;
+  QceObserveRowsArgs a;
+  a.B = B;
+  a.M = M;
+  a.N = N;
+  a.P = P;
+  a.noise = noise_kind;
+  a.seed = seed;
+  a.row_offset = row_offset;
+  a.S = S;
+  a.kind = kind;
+  a.nthr = nthr;
+  a.out = out_kind;
+  {
+    StreamScratch sc(st);
+    void* p;
+    // one upload: scales, cdf, pilot vector, thresholds, labels
+    const size_t n_thr = (size_t)S * nthr, n_lab = kind == 1 ? (size_t)S * n_levels : 0;
+    std::vector<double> tab;
+    tab.reserve(2 * (size_t)S + xk.size() + n_thr + n_lab);
+    tab.insert(tab.end(), noise_scales, noise_scales + S);
+    if (cdf) tab.insert(tab.end(), cdf, cdf + S);
+    else tab.insert(tab.end(), (size_t)S, 0.0);
+    if (P) tab.insert(tab.end(), xk.begin(), xk.end());
+    if (kind == 1) {
+      tab.insert(tab.end(), thresholds, thresholds + n_thr);
+      tab.insert(tab.end(), labels, labels + n_lab);
+    }
+    HIPCHK(sc.get(&p, sizeof(double) * tab.size()));
+    HIPCHK(hipMemcpyAsync(p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+    const double* dt = (const double*)p;
+    a.scales = dt;
+    a.cdf = cdf ? dt + S : nullptr;
+    a.xk = P ? (const double2*)(dt + 2 * S) : nullptr;
+    a.thr = kind == 1 ? dt + 2 * S + (P ? 2 * P : 0) : nullptr;
+    a.lab = kind == 1 ? a.thr + n_thr : nullptr;
+    a.A = nullptr;
+    if (A && !P) {
+      HIPCHK(sc.get(&p, sizeof(double2) * (size_t)M * N));
+      HIPCHK(hipMemcpyAsync(p, A, sizeof(double2) * (size_t)M * N, hipMemcpyHostToDevice, st));
+      a.A = (const double2*)p;
+    }
+    void* dout = out;
+    if (io == QCE_IO_HOST) {
+      HIPCHK(sc.get(&p, sizeof(double2) * nh));
+      HIPCHK(hipMemcpyAsync(p, h, sizeof(double2) * nh, hipMemcpyHostToDevice, st));
+      a.h = (const double2*)p;
+      a.w = nullptr;
+      if (noise_kind == 1) {
+        HIPCHK(sc.get(&p, sizeof(double2) * ny));
+        HIPCHK(hipMemcpyAsync(p, noise, sizeof(double2) * ny, hipMemcpyHostToDevice, st));
+        a.w = (const double2*)p;
+      }
+      a.idx_in = nullptr;
+      if (snr_index_in) {
+        HIPCHK(sc.get(&p, sizeof(int) * (size_t)B));
+        HIPCHK(hipMemcpyAsync(p, snr_index_in, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, st));
+        a.idx_in = (const int*)p;
+      }
+      HIPCHK(sc.get(&p, sizeof(int) * (size_t)B));
+      a.idx_out = (int*)p;
+      HIPCHK(sc.get(&dout, out_bytes));
+    } else {
+      a.h = (const double2*)h;
+      a.w = (const double2*)noise;
+      a.idx_in = snr_index_in;
+      a.idx_out = snr_index_out;
+    }
+    a.y = out_kind == QCE_OUT_Y ? (double2*)dout : nullptr;
+    a.feat = out_kind == QCE_OUT_Y ? nullptr : (float*)dout;
+    HIPCHK(qce_launch_observe_rows(a, st));
+    if (io == QCE_IO_HOST) {
+      HIPCHK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(snr_index_out, a.idx_out, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
+    }
+  }
+  if (io == QCE_IO_HOST) HIPCHK(hipStreamSynchronize(st));
+  return QCE_OK;
+}
+
 int qce_sq_error(const double* a, const double* b, int64_t n, double* out, int device, int io, void* stream) {
   if (n < 0 || !out || (n > 0 && (!a || !b))) return qce_set_error(QCE_EARG, "sq_error: bad arguments");
   if (io != QCE_IO_HOST && io != QCE_IO_DEVICE) return qce_set_error(QCE_EARG, "sq_error: bad io");

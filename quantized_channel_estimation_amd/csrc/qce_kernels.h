@@ -245,6 +245,35 @@ struct QceObserveArgs {
   double2* y;  // B x M
 };
 hipError_t qce_launch_observe(const QceObserveArgs& a, hipStream_t st);
+
+// Random-SNR observations and encoder features (qce_observe_rows.hip; utils.py:254-318, vae.py:46-53, :89-94)
+#define QCE_ROWS_MAX_SNRS 64
+#define QCE_ROWS_TABLE_LDS (32 * 1024)  // per-SNR quantiser tables are held in LDS up to this many bytes
+struct QceObserveRowsArgs {
+  long long B;
+  int M, N;
+  const double2* A;    // M x N dense, nullptr = identity (M == N) or kron(x, I_N) (P > 0)
+  int P;               // > 0: A = kron(x, I_N), M = P N, x in xk; 0 otherwise
+  const double2* xk;   // device, P entries
+  const double2* h;    // B x N
+  const double2* w;    // B x M supplied noise (noise == 1)
+  int noise;           // 0 none, 1 supplied, 2 generated (element counter (row_offset + b) M + m)
+  unsigned long long seed, row_offset;
+  int S;               // number of SNRs, <= QCE_ROWS_MAX_SNRS
+  const double* scales;  // device, S noise scales 10^(-snr / 20)
+  const double* cdf;     // device, S cumulative probabilities, or nullptr (uniform draw)
+  const int* idx_in;     // B supplied SNR indices, or nullptr (drawn: row counter row_offset + b)
+  int* idx_out;          // B
+  int kind;              // 0: 1 bit, 1: multi-bit, 2: unquantised
+  int nthr;              // L - 1 (multi-bit)
+  const double* thr;     // device, S x (L - 1)
+  const double* lab;     // device, S x L
+  int out;               // 0: y complex128 (B, M); 1: raw features, 2: DFT features, float (B, M / N, 2 N)
+  double2* y;
+  float* feat;
+};
+bool qce_observe_rows_feature_shape(int N);  // N in {16, 32, 64, 128, 256}
+hipError_t qce_launch_observe_rows(const QceObserveRowsArgs& a, hipStream_t st);
 int qce_sq_err_scratch();
 hipError_t qce_launch_sq_err(long long n, const double2* a, const double2* b, double* part, double* out,
                              hipStream_t st);
