@@ -296,6 +296,33 @@ int qce_rate_mf(const double* h_est, const double* h, int64_t B, int N, const do
 int qce_vae_estimate(int N, int P, const double* x_cplx, double snr_db, double n_bits, const void* logvar,
                      int logvar_is_f32, const double* y, int64_t B, double* h_out, int io, int device, void* stream);
 
+/* Training side of the VAE estimator (estimators/vae.py:280-281 and :312-365 vae_loss; csrc/qce_vae_train.hip),
+ * model-free.  All buffers are device memory (QCE_IO_DEVICE only), all three calls are asynchronous on `stream`
+ * (NULL = the null stream of `device`) and leave no status to read; refusals come before any launch.
+ * enc (B, 2L) float32 = [mu | s] is the encoder output (s = log_var_enc), 1 <= L <= 128 (more: QCE_ENOTIMPL).
+ *
+ * qce_vae_sample: z = mu + exp(s) eps -> z_out (B, L) float32, FP64 arithmetic rounded once.  eps_in (B, L) float32, or
+ * NULL: eps drawn on the device (Philox4x32-10 keyed by seed, a stream of its own; element (b, l) uses counter
+ * (row_offset + b) L + l, so rows [B1, B) generated with row_offset = B1 equal the one-shot rows).  eps_out (B, L)
+ * receives the eps used (may be NULL when eps_in is given).
+ * qce_vae_sample_bwd: grad_enc (B, 2L) = [grad_z | grad_z exp(s) eps]. */
+int qce_vae_sample(const float* enc, int64_t B, int L, const float* eps_in, uint64_t seed, uint64_t row_offset,
+                   float* z_out, float* eps_out, int device, void* stream);
+int qce_vae_sample_bwd(const float* enc, const float* eps, const float* grad_z, int64_t B, int L, float* grad_enc,
+                       int device, void* stream);
+
+/* qce_vae_elbo: rows_out[b] = the row ELBO l_b (float64) of vae_loss with zeromean=True, and in the same pass the
+ * gradient of the loss -mean_b l_b: grad_dec (B, N) float32 with respect to dec, grad_enc (B, 2L) float32 the direct
+ * (KL) part with respect to enc, both including the factor 1 / B.  dec (B, N) float32 = log_var_dec; target
+ * (n_target, 2N) float32 = [re | im]; row b uses target row index[b] (int32, clamped to [0, n_target)), or row b when
+ * index is NULL (then n_target >= B).  mode 0: 'genie' / 'noisy' (n_bits, snr_db ignored).  mode 1: 'real' with a
+ * uniform quantiser of n_bits in 1..8 or +INFINITY (none) and snr_db (n_target,) float64, row b at snr_db[index[b]].
+ * N: a power of two in [16, 256], else QCE_ENOTIMPL.  dec, target and grad_dec 16-byte aligned.  Equal inputs give
+ * bit-identical outputs (no atomics; the mean over rows is the caller's). */
+int qce_vae_elbo(const float* enc, const float* dec, const float* target, int64_t n_target, int64_t B, int N, int L,
+                 int mode, double n_bits, const int32_t* index, const double* snr_db, double* rows_out,
+                 float* grad_enc, float* grad_dec, int device, void* stream);
+
 /* Page-locked host memory (hipHostMalloc / hipHostFree).  QCE_IO_HOST calls DMA straight from / into page-locked
  * arrays (and from / into pageable ones they can register for the call): a caller that allocates its result arrays
  * here, and reuses them, saves the page faults of fresh pageable memory (the Python layer's result pool, _lib.py). */

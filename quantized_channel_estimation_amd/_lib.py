@@ -59,6 +59,11 @@ SIGNATURES = {
                                       ctypes.c_int, ctypes.c_int, _vp]),
     "qce_vae_estimate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, _vp,
                                         ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "qce_vae_sample": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
+                                      ctypes.c_int, _vp]),
+    "qce_vae_sample_bwd": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, _vp]),
+    "qce_vae_elbo": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "qce_model_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double]),
     "qce_estimate_assigned": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),
     "qce_estimate_ls": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),

@@ -41,6 +41,7 @@ hipError_t detect_structure(qce_model* m);  // at creation / set_params: is the 
 int check_status(qce_model* m, bool block);  // the last prepare's Cholesky status, once it is known (block: wait)
 int check_model(qce_model* m, bool need_prepared);
 int ensure_dense(qce_model* m, void* stream = nullptr);  // dense tables of a prepare that took the Fourier path
+double uniform_std_step(int nb);  // the unit-variance step of uniform_quantizer.py:6-21
 double uniform_step(double snr_db, int nb);
 
 #define HOST_SYNC_CHECK(m, st)                         \

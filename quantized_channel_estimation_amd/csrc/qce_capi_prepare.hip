@@ -117,10 +117,13 @@ hipError_t detect_structure(qce_model* m) {
 
 // Uniform quantiser step get_uniform_quant_step (uniform_quantizer.py:44-45) with standard_quantization_step
 // (:6-23): J. Max's table for n_bits <= 8, the asymptote 4 sqrt(b) 2^-b of Hui & Neuhoff beyond it (:15-21).
-double uniform_step(double snr_db, int nb) {
+double uniform_std_step(int nb) {
   static const double tbl[9] = {0, 1.596, 0.9957, 0.5860, 0.3352, 0.1881, 0.1041, 0.0569, 0.0308};
-  const double std_step = nb <= 8 ? tbl[nb] : 4.0 * sqrt((double)nb) * pow(2.0, -nb);
-  return sqrt((1.0 + pow(10.0, -snr_db / 10.0)) / 2.0) * std_step;
+  return nb <= 8 ? tbl[nb] : 4.0 * sqrt((double)nb) * pow(2.0, -nb);
+}
+
+double uniform_step(double snr_db, int nb) {
+  return sqrt((1.0 + pow(10.0, -snr_db / 10.0)) / 2.0) * uniform_std_step(nb);
 }
 
 int check_status(qce_model* m, bool block) {

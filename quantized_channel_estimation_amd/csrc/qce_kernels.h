@@ -353,6 +353,31 @@ struct QceVaeArgs {
   int TS;             // samples per workgroup (set by the launcher)
 };
 hipError_t qce_launch_vae(const QceVaeArgs& a, hipStream_t st);
+// VAE training: reparameterisation and the fused row ELBO with its gradient (qce_vae_train.hip; estimators/vae.py:280-281,
+// :312-365)
+#define QCE_VAE_MAX_LATENT 128
+struct QceVaeElboArgs {
+  long long B, T;      // rows of the batch; rows of t and entries of snr (the range of index)
+  int N, L;            // N a power of two in [16, 256], 1 <= L <= QCE_VAE_MAX_LATENT
+  int mode;            // 0: genie / noisy, 1: real
+  int n_bits;          // mode 1: 1..8 (uniform quantiser), 0 = no quantisation
+  double step;         // mode 1: the standard uniform step of n_bits
+  float sqrt_pi_f;     // sqrt(float(pi)) as float32: k2 = float(delta) / sqrt_pi_f
+  const float* enc;    // B x 2L = [mu | s]
+  const float* dec;    // B x N
+  const float* t;      // T x 2N = [tr | ti]
+  const int* index;    // B, or nullptr (row b uses target row b)
+  const double* snr;   // T (mode 1), dB
+  double* rows;        // B row ELBOs
+  float* g_enc;        // B x 2L
+  float* g_dec;        // B x N
+};
+bool qce_vae_train_shape(int N, int L);
+hipError_t qce_launch_vae_sample(const float* enc, const float* eps_in, long long B, int L, unsigned long long seed,
+                                 unsigned long long row_offset, float* z, float* eps_out, hipStream_t st);
+hipError_t qce_launch_vae_sample_bwd(const float* enc, const float* eps, const float* gz, long long B, int L,
+                                     float* g_enc, hipStream_t st);
+hipError_t qce_launch_vae_elbo(const QceVaeElboArgs& a, hipStream_t st);
 // Bussgang LS with column-orthogonal A_eff (qce_genie.hip; estimators/LS.py)
 hipError_t qce_launch_ls(long long B, int N, int M, const double2* y, const long long* comp, const double2* Aeff,
                          double2* h, hipStream_t st);

@@ -1,4 +1,5 @@
-// Device helpers shared by the observation kernels (qce_observe.hip, qce_observe_rows.hip): the counter-based
+// Device helpers shared by the observation kernels (qce_observe.hip, qce_observe_rows.hip) and, for the generator,
+// the VAE training kernels (qce_vae_train.hip): the counter-based
 // generator (Philox4x32-10 + Box-Muller in FP64) and the bit-exact quantiser of utils.py:189-203.
 #pragma once
 #include "qce_common.h"
@@ -10,6 +11,7 @@ constexpr double SQRT_HALF = 0x1.6a09e667f3bcdp-1;   // np.sqrt(0.5) (crandn, ut
 // third counter word: one domain per kind of draw, so the streams of one seed never share a counter
 constexpr uint32_t DOMAIN_NOISE = 0x51ED2701u;      // CN(0, 1) of complex element e
 constexpr uint32_t DOMAIN_SNR_INDEX = 0x51ED2702u;  // the SNR index of row b (qce_observe_rows.hip)
+constexpr uint32_t DOMAIN_VAE_EPS = 0x51ED2703u;    // N(0, 1) of latent element e (qce_vae_train.hip)
 
 // Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1)
 QCE_DEV uint4 philox(uint4 c, uint2 k) {

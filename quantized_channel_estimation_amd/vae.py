@@ -1,11 +1,23 @@
-"""VAE-parameterised Bussgang estimator, evaluation side (reference estimators/vae.py, driven by Bussgang_VAE.py).
+"""VAE-parameterised Bussgang estimator (reference estimators/vae.py, driven by Bussgang_VAE.py).
 
-``lmmse_from_decoder`` is the hot path: the reference's ``convert_dec_outputs`` (:376-431, zeromean=True) followed
-by ``lmmse`` (:368-369), computed by libqce.so in the Fourier domain (``qce_vae_estimate``, csrc/qce_vae.hip).
-``VAE_nbit`` wraps it with the reference's input preparation (:161-172) and the encoder / decoder forward of
-``DNN_VAE.forward_nosamp`` (:294-309), written as torch.nn.functional calls in float32 on the device (the
-reference's precision; this part is plumbing).  Training (``VAE_nbit.train``, ``vae_loss``) is not part of the
-package: the class consumes trained weights, under the reference's state-dict names.
+Evaluation.  ``lmmse_from_decoder`` is the hot path: the reference's ``convert_dec_outputs`` (:376-431,
+zeromean=True) followed by ``lmmse`` (:368-369), computed by libqce.so in the Fourier domain (``qce_vae_estimate``,
+csrc/qce_vae.hip).  ``VAE_nbit`` wraps it with the reference's input preparation (:161-172) and the encoder / decoder
+forward of ``DNN_VAE.forward_nosamp`` (:294-309), written as torch.nn.functional calls in float32 on the device (the
+reference's precision; this part is plumbing).
+
+Training.  ``VAE_nbit.train`` is the reference's loop (:15-154) on the device.  The layers stay torch.nn.functional
+calls under autograd; what lies between and around them is libqce.so (csrc/qce_vae_train.hip): ``reparameterize``
+(z = mu + exp(s) eps, eps drawn by the kernel) and ``elbo_loss`` (``vae_loss``, :312-365: the per-row ELBO in FP64 and
+its analytic gradient in the same pass, all three modes).  The per-epoch observations come from
+``observe.get_observation_nbit_randSNR(features=...)``.  Training is equivalent to the reference's, not bit-equal:
+torch's RNG streams for the initialisation, the shuffling and eps cannot be reproduced on another device, so the
+weights start from other draws of the same distributions (nn.Linear's / nn.Conv1d's uniform bounds), every step takes
+``batch_size`` distinct uniformly drawn rows as the reference's ``next(iter(dataloader))`` does, and eps is Philox
+noise.  Checkpoints carry the reference's keys and state-dict names.  In 'real' mode both the training and the
+validation observations are DFT features whatever ``fft_pre`` says; the reference transforms its training set always
+and its validation set only with ``fft_pre`` (:64-65, :100), so with ``fft_pre=False`` its validation loss is of another
+kind than its training loss, and than the validation loss here.
 
 The reference's behaviour is kept where it is observable, including its failures:
 
@@ -20,6 +32,8 @@ The reference's behaviour is kept where it is observable, including its failures
 Not emulated: ``pinv(hermitian=True)``'s eigenvalue cut-off.  The kernel solves with a Cholesky factorisation per
 DFT bin and raises ValueError when a bin is not positive definite.
 """
+import os
+
 import numpy as np
 
 from . import _lib, observe, rate as _rate
@@ -28,7 +42,11 @@ ZEROMEAN_MESSAGE = "too many values to unpack (expected 2)"
 LLOYD_MESSAGE = "can't assign a numpy.ndarray to a torch.ComplexDoubleTensor"
 BATCH1_MESSAGE = "too many indices for tensor of dimension 1"
 NORATE_MESSAGE = "'float' object has no attribute 'cpu'"
+HTEST_MESSAGE = "local variable 'dataloader_test' referenced before assignment"  # UnboundLocalError, train (:132)
 MAX_PILOTS = 4
+MAX_LATENT = 128       # latent_dim the training kernels take
+MAX_REAL_BITS = 8      # uniform quantisers of the 'real' loss
+LOSS_SKIP = 1000.0     # a step whose loss is NaN or above this is skipped (:120-121); epoch means are clipped to it
 EVAL_BATCH = 50  # the reference's DataLoader batch size in eval (:177)
 
 # the reference's float32 constants (torch.tensor(np.pi) is a float32 tensor; uniform_quantizer.py:79, :86)
@@ -107,6 +125,154 @@ def lmmse_from_decoder(y, log_var, snr, A=None, n_bits=1, quantizer_type="unifor
                                                 int(lv.dtype == np.float32), _lib.ptr(y), B, _lib.ptr(h),
                                                 _lib.IO_HOST, int(device), None))
     return h
+
+
+def _f32_device(t, name, ncols=None):
+    """t as a contiguous float32 CUDA tensor (B, ncols); anything else is an error (there is no CPU path)."""
+    import torch
+    if not _is_tensor(t) or not t.is_cuda:
+        raise TypeError(f"{name} must be a CUDA tensor (the training kernels run on the device only)")
+    if t.dtype != torch.float32 or t.dim() != 2 or (ncols is not None and t.shape[1] != ncols):
+        raise ValueError(f"{name} must be float32 (B, {ncols if ncols is not None else 'n'}), got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _dev_stream(t):
+    import torch
+    return t.device.index or 0, torch.cuda.current_stream(t.device).cuda_stream
+
+
+_FUNCTIONS = None
+
+
+def _functions():
+    """The two torch.autograd.Function classes over csrc/qce_vae_train.hip (built on first use: torch is imported
+    lazily throughout this module)."""
+    global _FUNCTIONS
+    if _FUNCTIONS is not None:
+        return _FUNCTIONS
+    import torch
+
+    class Reparameterize(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, enc, eps, seed, row_offset):
+            enc = enc.detach()
+            B, L = enc.shape[0], enc.shape[1] // 2
+            z = torch.empty((B, L), dtype=torch.float32, device=enc.device)
+            eps_out = torch.empty((B, L), dtype=torch.float32, device=enc.device)
+            dev, st = _dev_stream(enc)
+            _lib.check(_lib.load().qce_vae_sample(_lib.ptr(enc), B, L, _lib.ptr(eps), int(seed), int(row_offset),
+                                                  _lib.ptr(z), _lib.ptr(eps_out), dev, st))
+            ctx.save_for_backward(enc, eps_out)
+            ctx.mark_non_differentiable(eps_out)
+            return z, eps_out
+
+        @staticmethod
+        def backward(ctx, g_z, _g_eps):
+            enc, eps = ctx.saved_tensors
+            B, L = eps.shape
+            g_z = g_z.to(torch.float32).contiguous()
+            g_enc = torch.empty_like(enc)
+            dev, st = _dev_stream(enc)
+            _lib.check(_lib.load().qce_vae_sample_bwd(_lib.ptr(enc), _lib.ptr(eps), _lib.ptr(g_z), B, L,
+                                                      _lib.ptr(g_enc), dev, st))
+            return g_enc, None, None, None
+
+    class ElboLoss(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, enc, dec, target, mode, n_bits, snr_db, index):
+            enc, dec = enc.detach(), dec.detach()
+            B, N, L = dec.shape[0], dec.shape[1], enc.shape[1] // 2
+            rows = torch.empty(B, dtype=torch.float64, device=enc.device)
+            g_enc, g_dec = torch.empty_like(enc), torch.empty_like(dec)
+            dev, st = _dev_stream(enc)
+            _lib.check(_lib.load().qce_vae_elbo(_lib.ptr(enc), _lib.ptr(dec), _lib.ptr(target), target.shape[0], B, N, L,
+                                                mode, n_bits, _lib.ptr(index), _lib.ptr(snr_db), _lib.ptr(rows),
+                                                _lib.ptr(g_enc), _lib.ptr(g_dec), dev, st))
+            ctx.save_for_backward(g_enc, g_dec)
+            ctx.mark_non_differentiable(rows)
+            return (-rows.mean()).to(torch.float32), rows  # the mean in FP64, in torch's fixed reduction order
+
+        @staticmethod
+        def backward(ctx, g_loss, _g_rows):
+            g_enc, g_dec = ctx.saved_tensors  # the forward's gradients: no second pass over the data
+            return g_enc * g_loss, g_dec * g_loss, None, None, None, None, None
+
+    _FUNCTIONS = (Reparameterize, ElboLoss)
+    return _FUNCTIONS
+
+
+def reparameterize(enc_out, eps=None, *, seed=0, row_offset=0, return_eps=False):
+    """z (B, L) float32 = mu + exp(s) eps for the encoder output enc_out (B, 2L) = [mu | s] (float32, CUDA), with
+    autograd (``k_vae_sample`` / ``k_vae_sample_bwd``, FP64 arithmetic rounded once).  ``eps`` (B, L) float32, or None:
+    drawn on the device (Philox4x32-10 keyed by ``seed``; element (b, l) uses counter (row_offset + b) L + l, so rows
+    [B1, B) drawn with ``row_offset=B1`` equal the one-shot rows).  ``return_eps``: (z, eps)."""
+    enc = _f32_device(enc_out, "enc_out")
+    if enc.shape[1] % 2 or enc.shape[1] < 2:
+        raise ValueError(f"enc_out must be (B, 2 L), got {tuple(enc.shape)}")
+    L = enc.shape[1] // 2
+    if L > MAX_LATENT:
+        raise NotImplementedError(f"latent_dim up to {MAX_LATENT}, got {L}")
+    if eps is not None:
+        eps = _f32_device(eps, "eps", L)
+        if eps.shape[0] != enc.shape[0]:
+            raise ValueError(f"eps must be ({enc.shape[0]}, {L}), got {tuple(eps.shape)}")
+    z, e = _functions()[0].apply(enc, eps, int(seed), int(row_offset))
+    return (z, e) if return_eps else z
+
+
+def elbo_loss(enc_out, dec_out, target, *, mode, n_bits=1, snr_db=None, index=None, return_rows=False,
+              check_index=False):
+    """The reference's ``vae_loss`` (:312-365, zeromean=True) as a float32 scalar with autograd: -mean_b of the row
+    ELBOs, which ``k_vae_elbo`` computes in FP64 together with the gradient (``return_rows``: (loss, rows (B,)
+    float64)).  enc_out (B, 2L) = [mu | log_var_enc], dec_out (B, N) = log_var_dec, target (T, 2N) = [re | im], all
+    float32 CUDA tensors; row b uses target row (and SNR entry) ``index[b]`` (int32 (B,), values in [0, T), duplicates
+    allowed), or row b without ``index``.  mode 'genie' / 'noisy': the target is the channel's DFT features; 'real':
+    the observation's own features, with ``snr_db`` (T,) and a uniform quantiser of ``n_bits`` in 1..8 or inf.
+
+    The call is asynchronous, so ``index`` is not read on the host: the kernel clamps a value outside [0, T) to the
+    nearest valid row without an error, and loss and gradients are then those of the clamped rows.  ``check_index=True``
+    reads the index's range first (one host synchronisation) and raises ValueError instead."""
+    import torch
+    if mode not in ("genie", "noisy", "real"):
+        raise NotImplementedError("Choose a valid VAE-option.")
+    dec = _f32_device(dec_out, "dec_out")
+    B, N = dec.shape
+    pilot_vector(None, N)  # the shape refusal
+    enc = _f32_device(enc_out, "enc_out")
+    if enc.shape[0] != B or enc.shape[1] % 2 or enc.shape[1] < 2:
+        raise ValueError(f"enc_out must be ({B}, 2 L), got {tuple(enc.shape)}")
+    if enc.shape[1] // 2 > MAX_LATENT:
+        raise NotImplementedError(f"latent_dim up to {MAX_LATENT}, got {enc.shape[1] // 2}")
+    tgt = _f32_device(target.detach() if _is_tensor(target) else target, "target", 2 * N)
+    T = tgt.shape[0]
+    if index is not None:
+        if not _is_tensor(index) or not index.is_cuda or tuple(index.shape) != (B,):
+            raise ValueError(f"index must be a CUDA tensor ({B},)")
+        if T < 1:
+            raise ValueError("target is empty")
+        if check_index and B and (int(index.min()) < 0 or int(index.max()) >= T):
+            raise ValueError(f"index must lie in [0, {T})")
+        index = index.to(torch.int32).contiguous()
+    elif T < B:
+        raise ValueError(f"target has {T} rows for a batch of {B}")
+    nb = 1.0
+    if mode == "real":
+        nb = _nbits(n_bits)
+        if not np.isinf(nb) and (nb != int(nb) or nb < 1):
+            raise ValueError("n_bits must be an integer >= 1 or inf")
+        if not np.isinf(nb) and nb > MAX_REAL_BITS:
+            raise NotImplementedError(f"the 'real' loss covers uniform quantisers up to {MAX_REAL_BITS} bits")
+        if snr_db is None:
+            raise ValueError("mode 'real' needs snr_db, one value per target row")
+        snr_db = torch.as_tensor(snr_db, device=dec.device).to(torch.float64).reshape(-1).contiguous()
+        if snr_db.shape[0] != T:
+            raise ValueError(f"snr_db must have {T} entries, got {snr_db.shape[0]}")
+    else:
+        snr_db = None
+    loss, rows = _functions()[1].apply(enc, dec, tgt, int(mode == "real"), float(nb), snr_db, index)
+    return (loss, rows) if return_rows else loss
 
 
 def layer_shapes(params):
@@ -207,25 +373,182 @@ class VAE_nbit:
 
     def forward_nosamp(self, x):
         """Decoder log-variances (B, N) float32 for encoder inputs x: (B, P, 2N), or (B, 2N) in 'genie' mode."""
-        import torch.nn.functional as Fn
         if self._w is None:
             raise RuntimeError("no weights: call load_state_dict or from_checkpoint first")
+        x = self._encode(x)
+        return self._decode(x[:, :x.shape[-1] // 2])
+
+    def _encode(self, x, sums=False):
+        """Encoder output (B, 2L) = [mu | log_var_enc]: the pilot convolutions (not in 'genie' mode) and enc.
+        ``sums``: the pilot convolutions (kernel size 1) written as weighted sums over the pilots.  The training
+        forward uses that form: the library behind conv1d accumulates its weight gradient in an order that changes
+        from call to call, and a training step is to be reproducible to the bit."""
+        import torch.nn.functional as Fn
         p, w = self.params, self._w
         nl = int(p["n_layers"])
         if p["vae_mode"] != "genie":
             for i in range(int(p.get("n_pilot_convs", 0))):
-                x = Fn.relu(Fn.conv1d(x, w[f"pre_pilot.conv{i}.weight"], w[f"pre_pilot.conv{i}.bias"]))
+                cw, cb = w[f"pre_pilot.conv{i}.weight"], w[f"pre_pilot.conv{i}.bias"]
+                if sums:  # (B, out, in, 2N) summed over in
+                    x = Fn.relu((cw[None, :, :, 0, None] * x[:, None, :, :]).sum(2) + cb[None, :, None])
+                else:
+                    x = Fn.relu(Fn.conv1d(x, cw, cb))
             x = x.squeeze(1)
         for i in range(nl):
             x = Fn.linear(x, w[f"enc.linear{i}.weight"], w[f"enc.linear{i}.bias"])
             if i < nl - 1:
                 x = Fn.relu(x)
-        x = x[:, :x.shape[-1] // 2]
+        return x
+
+    def _decode(self, x):
+        import torch.nn.functional as Fn
+        w = self._w
+        nl = int(self.params["n_layers"])
         for i in range(nl):
             x = Fn.linear(x, w[f"dec.linear{i}.weight"], w[f"dec.linear{i}.bias"])
             if i < nl - 1:
                 x = Fn.relu(x)
         return x
+
+    def forward(self, x, eps=None, *, seed=0, row_offset=0):
+        """The sampling forward of ``DNN_VAE.forward`` (:272-291): (enc (B, 2L) = [mu | log_var_enc], dec (B, N) =
+        log_var_dec) with z = ``reparameterize(enc, eps, seed=..., row_offset=...)`` between encoder and decoder."""
+        if self._w is None:
+            raise RuntimeError("no weights: call load_state_dict, from_checkpoint or train first")
+        enc = self._encode(x, sums=True)
+        return enc, self._decode(reparameterize(enc, eps, seed=seed, row_offset=row_offset))
+
+    # ------------------------------------------------------------------ training
+    def _snr_scaling(self):
+        p = self.params
+        if not p.get("snr_scale", False):
+            return None
+        s = np.linspace(1, p["snr_scale_fac"], len(p["snrs"]))  # :18-20
+        return s / np.sum(s)
+
+    def _check_trainable(self, h_test):
+        """The refusals of ``train``, before anything is uploaded."""
+        p = self.params
+        if not p.get("zeromean", True):
+            raise ValueError(ZEROMEAN_MESSAGE)
+        N, P, L = int(p["n_antennas"]), int(p["n_pilots"]), int(p["latent_dim"])
+        pilot_vector(None, N)
+        if L < 1 or L > MAX_LATENT:
+            raise NotImplementedError(f"latent_dim must lie in [1, {MAX_LATENT}], got {L}")
+        if p["vae_mode"] == "real":
+            nb = _nbits(p["n_bits"])
+            if not np.isinf(nb) and p.get("quantizer_type", "uniform") != "uniform":
+                raise NotImplementedError("the 'real' loss needs the uniform quantiser's Bussgang gain (:328-331)")
+            if not np.isinf(nb) and nb > MAX_REAL_BITS:
+                raise NotImplementedError(f"the 'real' loss covers uniform quantisers up to {MAX_REAL_BITS} bits")
+            if P > 1:
+                raise NotImplementedError("vae_mode 'real' trains with one pilot: the reference transforms the whole "
+                                          "row of length P N and its encoder takes 2 N inputs")
+        if h_test is None:
+            raise UnboundLocalError(HTEST_MESSAGE)  # the reference's first validation pass (:132)
+
+    def _init_weights(self, gen):
+        """Fresh leaf tensors under the reference's names, drawn as nn.Linear / nn.Conv1d (kernel size 1) draw
+        theirs: weight and bias uniform in +-1 / sqrt(fan_in)."""
+        import torch
+        dev = self._device()
+        w = {}
+        for name, shape in layer_shapes(self.params).items():
+            fan_in = shape[1] if name.endswith(".weight") else w[name[:-4] + "weight"].shape[1]
+            bound = 1.0 / np.sqrt(fan_in)
+            t = (torch.rand(shape, generator=gen, device=dev, dtype=torch.float32) * 2 - 1) * bound
+            w[name] = t.requires_grad_(True)
+        self._w = w
+
+    def _train_data(self, h_dev, snr_list, seed, row_offset):
+        """(encoder input, target, per-row SNRs) of one epoch for the channels h_dev, on the device."""
+        p = self.params
+        N, mode = int(p["n_antennas"]), p["vae_mode"]
+        if mode == "genie":
+            f = observe.encoder_features(h_dev, N, True).reshape(-1, 2 * N)
+            return f, f, None
+        feat = "fft" if (mode == "real" or p.get("fft_pre", True)) else "raw"
+        x, snrs = observe.get_observation_nbit_randSNR(h_dev, snr_list, p.get("A"), p["n_bits"], p.get("quantizer"),
+                                                       self._snr_scaling(), seed=seed, row_offset=row_offset,
+                                                       features=feat)
+        if mode == "real":
+            return x, x.reshape(-1, 2 * N), snrs
+        return x, None, None
+
+    def train(self, h_train, h_test, snr_list, *, seed=0, file_vae=None):
+        """The reference's training loop (:15-154) on the device; returns (losses_all, losses_all_test), the clipped
+        epoch means of the training and validation loss.  ``params`` additionally needs lr, batch_size, epochs,
+        snr_scale (and snr_scale_fac, snrs), and for the default checkpoint name sim_id, model_type, n_paths, n_train.
+        The trained weights stay in the object (``forward_nosamp`` / ``estimate_from_y`` work at once) and are saved
+        after every epoch to ``file_vae`` (default: the reference's name pattern), a file ``from_checkpoint`` reads.
+        ``seed`` keys every draw: initial weights, batches, observations and eps."""
+        self._check_trainable(h_test)
+        import torch
+        p = self.params
+        mode, N, bs = p["vae_mode"], int(p["n_antennas"]), int(p["batch_size"])
+        dev = self._device()
+        h_tr, h_te = (torch.as_tensor(h if _is_tensor(h) else np.array(h, dtype=np.complex128), device=dev)
+                      .to(torch.complex128).reshape(-1, N).contiguous() for h in (h_train, h_test))
+        n_train, n_test, epochs = h_tr.shape[0], h_te.shape[0], int(p["epochs"])
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        self._init_weights(gen)
+        opti = torch.optim.Adam(list(self._w.values()), lr=p["lr"])
+        if file_vae is None:
+            file_vae = (f'results/vae/saves/VAE{p["vae_mode"]}_{p["sim_id"]}_{p["model_type"]}_paths={p["n_paths"]}_ant='
+                        f'{p["n_antennas"]}_ntrain={p["n_train"]}.pt')  # :76-78
+        p["file_vae"] = file_vae
+        nb = _nbits(p["n_bits"])
+
+        t_train = t_test = None
+        if mode == "noisy":
+            t_train = observe.encoder_features(h_tr, N, True).reshape(-1, 2 * N)
+            t_test = observe.encoder_features(h_te, N, True).reshape(-1, 2 * N)
+        # validation observations: drawn once, from rows beyond every training epoch's
+        x_te, tt, snr_te = self._train_data(h_te, snr_list, seed, epochs * n_train)
+        t_test = tt if tt is not None else t_test
+        x_tr, tt, snr_tr = self._train_data(h_tr, snr_list, seed, 0) if mode == "genie" else (None, None, None)
+        t_train = tt if tt is not None else t_train
+
+        drawn = [0]  # rows of eps drawn so far: every forward takes fresh counters
+
+        def loss_of(x_all, t_all, snr_all, n_rows):
+            # the first batch of a fresh shuffle (next(iter(dataloader))): bs distinct, uniformly drawn rows
+            idx = torch.randperm(n_rows, generator=gen, device=dev)[:bs]
+            enc, dec = self.forward(x_all.index_select(0, idx), seed=seed, row_offset=drawn[0])
+            drawn[0] += bs
+            return elbo_loss(enc, dec, t_all, mode=mode, n_bits=nb, snr_db=snr_all, index=idx.to(torch.int32))
+
+        losses_all, losses_all_test = [], []
+        for epoch in range(epochs):
+            if mode != "genie":
+                x_tr, tt, snr_tr = self._train_data(h_tr, snr_list, seed, epoch * n_train)
+                t_train = tt if tt is not None else t_train
+            loss_epoch = []
+            for _ in range(n_train // bs):
+                opti.zero_grad()
+                loss = loss_of(x_tr, t_train, snr_tr, n_train)
+                val = float(loss.detach())  # the skip rule's host read (:120)
+                if np.isnan(val) or val > LOSS_SKIP:
+                    continue
+                loss.backward()
+                opti.step()
+                loss_epoch.append(val)
+            if not loss_epoch or np.isnan(np.mean(loss_epoch)):
+                continue
+            losses_all.append(np.clip(np.mean(loss_epoch), -np.inf, LOSS_SKIP))
+            with torch.no_grad():
+                loss_test = [loss_of(x_te, t_test, snr_te, n_test) for _ in range(n_test // bs)]
+                loss_test = torch.stack(loss_test).cpu().numpy().astype(np.float64) if loss_test else np.full(1, np.nan)
+                losses_all_test.append(np.clip(np.mean(loss_test), -np.inf, LOSS_SKIP))
+            parent = os.path.dirname(file_vae)
+            if parent:
+                os.makedirs(parent, exist_ok=True)
+            torch.save({"model": {k: v.detach() for k, v in self._w.items()}, "optim": opti.state_dict(),
+                        "loss_all": losses_all, "epoch": epoch, "params": p}, file_vae)
+        for v in self._w.values():
+            v.requires_grad_(False)
+        return losses_all, losses_all_test
 
     def _estimate(self, y, snr, h):
         import torch
