@@ -119,6 +119,12 @@ int run_f64(qce_model* m, const double2* dy, long long B, double2* h, double* om
   a.pa = m->fp_a.p;
   a.pk = pk;
   a.shift = shift;
+  if (g3 == 1) {
+    if (const long long nscr = qce_f64g_scratch_doubles(m->MP, m->NP, m->K, nwg)) {
+      HIPCHK(m->fp_scr.ensure((size_t)nscr));
+      a.pscr = m->fp_scr.p;
+    }
+  }
   {
     const char* wv = getenv("QCE_F64_WAVES");  // 8 (default): two waves per SIMD where M, N <= 64
     a.waves = (wv && atoi(wv) == 4) ? 4 : 8;

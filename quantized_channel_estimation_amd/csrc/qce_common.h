@@ -61,6 +61,20 @@ QCE_DEV void lds_dma16(const void* src, const void* lds_dst) {
   const unsigned dst = (unsigned)(unsigned long)(__attribute__((address_space(3))) const void*)lds_dst;
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory", "m0");
 }
+// The same DMA with the wave-uniform part of the source in an SGPR pair and the lane's part in one 32-bit VGPR
+// (lane l reads sbase + voff; voff = 16 l for a contiguous 1 KB piece).  A ring refill's pieces then differ only in
+// sbase, which the scalar unit advances: no 64-bit VALU address arithmetic per piece.
+QCE_DEV void lds_dma16(const void* sbase, unsigned voff, const void* lds_dst) {
+  const unsigned dst = (unsigned)(unsigned long)(__attribute__((address_space(3))) const void*)lds_dst;
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(dst)
+               : "memory", "m0");
+}
+// a wave-uniform pointer as the compiler's scalar value (for the SGPR-base form above)
+QCE_DEV const char* uniform_ptr(const char* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (const char*)(((unsigned long long)hi << 32) | lo);
+}
 #pragma clang diagnostic pop
 
 #include "../../include/qce.h"

@@ -168,12 +168,9 @@ __global__ __launch_bounds__(64) void k_pack_f64all(int M, int N, int MP, int NP
 // k-steps 2u, 2u + 1 in the order j = 0: Ls s0, Lm s0; 1: Lp s0, Ls s1; 2: Lm s1, Lp s1), Ls = Re + Im, Lm = -2 Im,
 // Lp = 2 Re of the complex entry; lane (r, g) = row 16 T + r, column 4 s + g.  Mean block: (-q0 re, -q0 im) in
 // k = 0; bias block: (b re, b im).
-__global__ __launch_bounds__(64) void k_pack_f64g(int M, int N, int MP, int NP, int has_mean, int bpc,
-                                                  const double2* __restrict__ Linv, const double2* __restrict__ W,
-                                                  const double2* __restrict__ q0, const double2* __restrict__ bvec,
-                                                  double* __restrict__ pack) {
-  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
-  const BlockInfo3 bi = block_info3_rt(MP, NP, has_mean ? 1 : 0, b);
+__device__ __forceinline__ double2 pack_f64g_entry(const BlockInfo3 bi, int k, int lane, int M, int N,
+                                                   const double2* __restrict__ Linv, const double2* __restrict__ W,
+                                                   const double2* __restrict__ q0, const double2* __restrict__ bvec) {
   const int r = lane & 15, gk = lane >> 4;
   const int i = 16 * bi.T + r;
   const bool isL = bi.kind <= 1;
@@ -201,7 +198,29 @@ __global__ __launch_bounds__(64) void k_pack_f64g(int M, int N, int MP, int NP, 
     v[0] = z.x;
     v[1] = z.y;
   }
-  *reinterpret_cast<double2*>(pack + (((long long)k * bpc + b) * 64 + lane) * 2) = make_double2(v[0], v[1]);
+  return make_double2(v[0], v[1]);
+}
+__global__ __launch_bounds__(64) void k_pack_f64g(int M, int N, int MP, int NP, int has_mean, int bpc,
+                                                  const double2* __restrict__ Linv, const double2* __restrict__ W,
+                                                  const double2* __restrict__ q0, const double2* __restrict__ bvec,
+                                                  double* __restrict__ pack) {
+  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+  const BlockInfo3 bi = block_info3_rt(MP, NP, has_mean ? 1 : 0, b);
+  *reinterpret_cast<double2*>(pack + (((long long)k * bpc + b) * 64 + lane) * 2) =
+      pack_f64g_entry(bi, k, lane, M, N, Linv, W, q0, bvec);
+}
+// Two-pass layout (k_est_all_f64g2): region GL[K] of bpc_l blocks per component, then region GW[K] of bpc_w; the
+// blocks of a region in the single-pass order, each region padded to whole ring chunks of the one size both share
+// (f64g2_cb).
+__global__ __launch_bounds__(64) void k_pack_f64g2(int M, int N, int MP, int NP, int has_mean, int bpc_l, int bpc_w,
+                                                   const double2* __restrict__ Linv, const double2* __restrict__ W,
+                                                   const double2* __restrict__ q0, const double2* __restrict__ bvec,
+                                                   double* __restrict__ pack) {
+  const int b = blockIdx.x, k = blockIdx.y, K = gridDim.y, lane = threadIdx.x;
+  const int pass = b < bpc_l ? 0 : 1;
+  const BlockInfo3 bi = block_info3_pass(MP, NP, has_mean ? 1 : 0, pass, pass ? b - bpc_l : b);
+  const long long blk = pass ? (long long)K * bpc_l + (long long)k * bpc_w + (b - bpc_l) : (long long)k * bpc_l + b;
+  *reinterpret_cast<double2*>(pack + (blk * 64 + lane) * 2) = pack_f64g_entry(bi, k, lane, M, N, Linv, W, q0, bvec);
 }
 
 // ---------------------------------------------------------------------------
@@ -209,7 +228,10 @@ __global__ __launch_bounds__(64) void k_pack_f64g(int M, int N, int MP, int NP, 
 // ---------------------------------------------------------------------------
 namespace {
 int blocks_per_comp(int MP, int NP, int hm) { return f64_pack_blocks(MP, NP, hm ? 1 : 0); }
-int blocks_per_comp_g(int MP, int NP, int hm) { return f64g_bpc(f64g_blocks(MP, NP, hm ? 1 : 0)); }
+int blocks_per_comp_g(int MP, int NP, int hm) {
+  if (f64g_two_pass(MP, NP)) return f64g2_bpc_l(MP, NP, hm ? 1 : 0) + f64g2_bpc_w(MP, NP, hm ? 1 : 0);
+  return f64g_bpc(f64g_blocks(MP, NP, hm ? 1 : 0));
+}
 }  // namespace
 
 // the 3M kernel covers padded M, N in {16, 32, 64} (8 waves x 16 samples; QCE_F64_3M=0 keeps the 4M kernel)
@@ -219,12 +241,21 @@ bool qce_f64g_shape(int MP, int NP) {
   auto ok = [](int v) { return v == 16 || v == 32 || v == 64; };
   return ok(MP) && ok(NP);
 }
-int qce_f64g_waves() { return QCE_F64G_NW; }
+int qce_f64g_waves() { return F64G_NW; }
+long long qce_f64g_scratch_doubles(int MP, int NP, int K, long long nwg) {
+  return f64g_two_pass(MP, NP) ? nwg * K * 16LL * F64G_NW : 0;
+}
 long long qce_pack_f64g_bytes(int MP, int NP, int has_mean) { return (long long)blocks_per_comp_g(MP, NP, has_mean) * 1024; }
 hipError_t qce_launch_pack_f64g(int K, int M, int N, int MP, int NP, int has_mean, const double2* Linv,
                                 const double2* W, const double2* q0, const double2* bvec, double* pack,
                                 hipStream_t st) {
   const int bpc = blocks_per_comp_g(MP, NP, has_mean);
+  if (f64g_two_pass(MP, NP)) {
+    const int bl = f64g2_bpc_l(MP, NP, has_mean ? 1 : 0), bw = f64g2_bpc_w(MP, NP, has_mean ? 1 : 0);
+    hipLaunchKernelGGL(k_pack_f64g2, dim3(bpc, K), dim3(64), 0, st, M, N, MP, NP, has_mean, bl, bw, Linv, W, q0,
+                       bvec, pack);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_pack_f64g, dim3(bpc, K), dim3(64), 0, st, M, N, MP, NP, has_mean, bpc, Linv, W, q0, bvec,
                      pack);
   return hipGetLastError();
@@ -270,7 +301,7 @@ hipError_t qce_launch_est_f64(const QceF64Args& a, bool out_partial, hipStream_t
     default: e = hipErrorInvalidValue;
   }
   if (e != hipSuccess) return e;
-  const long long TS = a.g3 == 2 ? 64LL : (a.g3 ? 16LL * QCE_F64G_NW : qce_f64_tile(a.MP, a.NP));
+  const long long TS = a.g3 == 2 ? 64LL : (a.g3 ? 16LL * F64G_NW : qce_f64_tile(a.MP, a.NP));
   const long long tiles = (a.B + TS - 1) / TS;
   const long long tail0 = (long long)a.R * a.nwg;
   if (a.L > 0 && tiles > tail0) {  // some tail tile may be cut between workgroups

@@ -33,6 +33,10 @@
 // Scheduling as k_est_all_f64's 8-wave shape: one workgroup = 8 waves (two per SIMD) x 16 samples, the tables
 // streamed through an LDS ring of NSLOT chunks (global_load_lds DMA), persistent grid with a stream-K tail whose cut
 // tiles leave FP64 partials for k_merge_f64 (same format).
+//
+// Padded M = 64 runs the same products in two passes per segment (k_est_all_f64g2, qce_f64g2_kernel.h, included
+// below: log-prob pass, one exact softmax, filter pass; its table is two regions GL[K], GW[K]); the single-pass
+// kernel of this file serves padded M = 16 and 32.
 #pragma once
 #include "qce_f64_kernel.h"
 
@@ -41,24 +45,11 @@
 #ifndef QCE_F64G_E
 #define QCE_F64G_E 2
 #endif
-// waves per workgroup: 8 (one 8-wave workgroup per CU, two waves per SIMD, one ring of <= 144 KB) or 4 (two
-// 4-wave workgroups per CU, each with its own ring of <= 72 KB: a workgroup's ring barriers then sync one wave per
-// SIMD, the other workgroup's wave keeps the SIMD's MFMA pipe busy)
-#ifndef QCE_F64G_NW
-#define QCE_F64G_NW 8
-#endif
+// waves per workgroup: one 8-wave workgroup per CU, two waves per SIMD, one ring of <= 144 KB
+constexpr int F64G_NW = 8;
 // ring chunk (blocks); 0 = chosen from the block count (f64_cb)
 #ifndef QCE_F64G_CB
 #define QCE_F64G_CB 0
-#endif
-// waves 4-7 (the second wave of every SIMD) consume the ring LAG chunks behind waves 0-3, so the two waves of a SIMD
-// reach their softmax and GL folds at different times (the ring keeps LAG more chunks; 0 = lockstep)
-#ifndef QCE_F64G_LAG
-#define QCE_F64G_LAG 0
-#endif
-// 1: libm exp for the softmax weights (A/B builds)
-#ifndef QCE_F64G_LIBM_EXP
-#define QCE_F64G_LIBM_EXP 0
 #endif
 
 namespace {
@@ -88,11 +79,46 @@ QCE_DEV double exp_tab64(double x, const double* __restrict__ tab) {
 
 // ring chunk (blocks) and padded blocks per component of the 3M table: shared by the kernel and k_pack_f64g
 constexpr __host__ __device__ int f64g_cb(int blocks) {
-  return QCE_F64G_CB > 0 ? QCE_F64G_CB : (QCE_F64G_NW == 8 ? f64_cb(blocks, 0, 1) : 24);
+  return QCE_F64G_CB > 0 ? QCE_F64G_CB : f64_cb(blocks, 0, 1);
 }
 constexpr __host__ __device__ int f64g_bpc(int blocks) { return (blocks + f64g_cb(blocks) - 1) / f64g_cb(blocks) * f64g_cb(blocks); }
 constexpr __host__ __device__ int f64g_blocks(int MP, int NP, int hmi) {
   return 3 * (MP / 16) * (MP / 16 + 1) + hmi * (MP / 16) + 3 * (MP / 8) * (NP / 16) + hmi * (NP / 16);
+}
+
+// ---- two-pass form (k_est_all_f64g2, qce_f64g2_kernel.h): GL[K] then GW[K] regions, one chunk size for both ----
+// 0: single-pass kernel for every shape; 1: two passes where padded M = 64 (the GL and GW parts of a component then
+// fill whole chunks with <= 12 pad blocks; at padded 16 / 32 each part would pad to a chunk of its own, doubling the
+// ring's barriers); 2: two passes for every shape (A/B builds)
+#ifndef QCE_F64G_TWO_PASS
+#define QCE_F64G_TWO_PASS 1
+#endif
+constexpr __host__ __device__ bool f64g_two_pass(int MP, int) {
+  return QCE_F64G_TWO_PASS == 2 || (QCE_F64G_TWO_PASS == 1 && MP == 64);
+}
+constexpr __host__ __device__ int f64g_gl_blocks(int MP, int hmi) { return 3 * (MP / 16) * (MP / 16 + 1) + hmi * (MP / 16); }
+constexpr __host__ __device__ int f64g_gw_blocks(int MP, int NP, int hmi) { return 3 * (MP / 8) * (NP / 16) + hmi * (NP / 16); }
+// ring chunk (blocks) shared by the two regions: least padding of both plus the barrier cost of a chunk (as f64_cb)
+constexpr __host__ __device__ int f64g2_cb(int gl, int gw) {
+  int best = 16;
+  double best_cost = 1e30;
+  for (int cb = 16; cb <= 48; cb += 8) {
+    const int pad = (gl + cb - 1) / cb * cb - gl + (gw + cb - 1) / cb * cb - gw;
+    const double cost = (double)pad / (gl + gw) + 2.0 / cb;
+    if (cost < best_cost - 1e-12) {
+      best_cost = cost;
+      best = cb;
+    }
+  }
+  return best;
+}
+constexpr __host__ __device__ int f64g2_bpc_l(int MP, int NP, int hmi) {
+  const int cb = f64g2_cb(f64g_gl_blocks(MP, hmi), f64g_gw_blocks(MP, NP, hmi));
+  return (f64g_gl_blocks(MP, hmi) + cb - 1) / cb * cb;
+}
+constexpr __host__ __device__ int f64g2_bpc_w(int MP, int NP, int hmi) {
+  const int cb = f64g2_cb(f64g_gl_blocks(MP, hmi), f64g_gw_blocks(MP, NP, hmi));
+  return (f64g_gw_blocks(MP, NP, hmi) + cb - 1) / cb * cb;
 }
 
 template <int MP, int NP, bool HM>
@@ -107,11 +133,8 @@ struct F64G3 {
   static constexpr int GL_BLOCKS = gl_off(NTL);
   static constexpr int GW_BLOCKS = 3 * KU * NTW + HMI * NTW;
   static constexpr int BLOCKS = GL_BLOCKS + GW_BLOCKS;
-  static constexpr int NWG = QCE_F64G_NW;  // waves per workgroup
-  static constexpr int LDS_KB = NWG == 8 ? 144 : 72;
   static constexpr int CB = f64g_cb(BLOCKS);
-  static constexpr int LAG = QCE_F64G_LAG;
-  static constexpr int NSLOT = LDS_KB / CB < 8 ? LDS_KB / CB : 8;
+  static constexpr int NSLOT = 144 / CB < 8 ? 144 / CB : 8;  // ring of <= 144 KB
   static constexpr int CHUNK = CB * 1024;
   static constexpr int BPC = f64g_bpc(BLOCKS);
   static_assert(BLOCKS == f64g_blocks(MP, NP, HMI), "block count");
@@ -141,11 +164,17 @@ __host__ __device__ constexpr BlockInfo3 block_info3_rt(int MP, int NP, int hmi,
   if (r < 3 * KU * NTW + hmi * NTW) return BlockInfo3{3, r - 3 * KU * NTW, 0, 0};
   return BlockInfo3{4, 0, 0, 0};
 }
+// block b of a component's GL (pass 0) or GW (pass 1) region in the two-pass layout
+__host__ __device__ constexpr BlockInfo3 block_info3_pass(int MP, int NP, int hmi, int pass, int b) {
+  const int gl = f64g_gl_blocks(MP, hmi);
+  if (pass == 0) return b < gl ? block_info3_rt(MP, NP, hmi, b) : BlockInfo3{4, 0, 0, 0};
+  return block_info3_rt(MP, NP, hmi, gl + b);
+}
 
 }  // namespace
 
 template <int MP, int NP, bool HM, bool OUT_PARTIAL>
-__global__ __launch_bounds__(QCE_F64G_NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_est_all_f64g(long long B, int M, int N, int K, int R, long long L,
+__global__ __launch_bounds__(F64G_NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_est_all_f64g(long long B, int M, int N, int K, int R, long long L,
                                                       const double2* __restrict__ y, const char* __restrict__ pack,
                                                       const double* __restrict__ cconst, double2* __restrict__ h,
                                                       double* __restrict__ om, double* __restrict__ os,
@@ -154,15 +183,14 @@ __global__ __launch_bounds__(QCE_F64G_NW * 64) __attribute__((amdgpu_waves_per_e
                                                       double* __restrict__ pk, const double* __restrict__ shift,
                                                       unsigned long long* __restrict__ stamps) {
   using G = F64G3<MP, NP, HM>;
-  constexpr int NW = G::NWG;       // waves of 16 samples; two per SIMD (one or two workgroups per CU)
+  constexpr int NW = F64G_NW;      // waves of 16 samples; two per SIMD
   constexpr int TS = NW * 16;     // samples per tile
   constexpr int LPW = G::CB / NW;  // global_load_lds pieces per wave per chunk
   constexpr int E = QCE_F64G_E;
   constexpr double RESCALE = 32.0;  // lazy max: rescale only when lp exceeds m by this
   static_assert(G::CB % NW == 0, "chunk split");
   static_assert(E < G::CB, "the prefetch window must stay inside one chunk");
-  static_assert(G::NSLOT >= 3 + G::LAG, "ring depth");
-  static_assert(G::LAG == 0 || NW == 8, "lag: two waves per SIMD in one workgroup");
+  static_assert(G::NSLOT >= 3, "ring depth");
   __shared__ __attribute__((aligned(16))) char lds[G::NSLOT * G::CHUNK];
   __shared__ double etab[32];  // 2^(j/32) for exp_tab64
 
@@ -197,31 +225,21 @@ __global__ __launch_bounds__(QCE_F64G_NW * 64) __attribute__((amdgpu_waves_per_e
   auto refill_pieces = [&](int lo, int hi) {
     for (int i = lo; i < hi; ++i) lds_dma16(rsrc + i * NW * 1024, lds + rdst + i * NW * 1024);
   };
-  // chunk k lands by barrier k: at barrier k the slot of chunk k - LAG - 2 is free (the lagging waves are done
-  // with it) and takes chunk k + NSLOT - LAG - 2
+  // chunk k lands by barrier k: at barrier k the slot of chunk k - 2 is free and takes chunk k + NSLOT - 2
   auto boundary_wait = [&]() {
-    wait_vmcnt<(G::NSLOT - 3 - G::LAG) * LPW>();
+    wait_vmcnt<(G::NSLOT - 3) * LPW>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     F64_STAMP(3);
   };
 #pragma unroll 1
-  for (int j = 0; j < G::NSLOT - 2 - G::LAG; ++j) {
+  for (int j = 0; j < G::NSLOT - 2; ++j) {
     refill_begin();
     refill_pieces(0, LPW);
   }
   boundary_wait();  // chunk 0
   refill_begin();
   refill_pieces(0, LPW);
-  const bool lagging = G::LAG > 0 && wave >= NW / 2;  // wave-uniform
-  if (lagging) {  // the lagging waves' first LAG barriers: refills only
-#pragma unroll 1
-    for (int j = 0; j < G::LAG; ++j) {
-      boundary_wait();
-      refill_begin();
-      refill_pieces(0, LPW);
-    }
-  }
   int cstream = 0;
 
   for (long long seg = 0; seg < nseg; ++seg) {
@@ -403,11 +421,7 @@ __global__ __launch_bounds__(QCE_F64G_NW * 64) __attribute__((amdgpu_waves_per_e
                   oi[T] *= al;
                 }
               }
-#if QCE_F64G_LIBM_EXP
-              p = (lp == QCE_NEG_INF) ? 0.0 : exp(lp - m);
-#else
               p = (lp == QCE_NEG_INF) ? 0.0 : exp_tab64(lp - m, etab);
-#endif
               ssum += p;
               F64_STAMP(1);
             }
@@ -470,24 +484,25 @@ __global__ __launch_bounds__(QCE_F64G_NW * 64) __attribute__((amdgpu_waves_per_e
       }
     }
   }
-  if (G::LAG > 0 && !lagging) {  // the leading waves' last LAG barriers, matching the lagging waves' first ones
-#pragma unroll 1
-    for (int j = 0; j < G::LAG; ++j) {
-      boundary_wait();
-      refill_begin();
-      refill_pieces(0, LPW);
-    }
-  }
   F64_STAMP(5);
   F64_STAMP_FLUSH
   wait_vmcnt<0>();  // drain the (dummy) ring prefetches before the workgroup retires
 }
 
+#include "qce_f64g2_kernel.h"
+
 template <int MP, int NP, bool HM, bool OP>
 hipError_t qce_f64g_launch_t(const QceF64Args& a, hipStream_t st) {
-  hipLaunchKernelGGL((k_est_all_f64g<MP, NP, HM, OP>), dim3((unsigned)a.nwg), dim3(QCE_F64G_NW * 64), 0, st, a.B, a.M, a.N, a.K,
-                     a.R, a.L, a.y, a.pack, a.cconst, a.h, a.om, a.os, a.oa, a.pm, a.ps, a.pa, a.pk, a.shift,
-                     a.stamps);
+  if constexpr (f64g_two_pass(MP, NP)) {
+    if (!a.pscr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_est_all_f64g2<MP, NP, HM, OP>), dim3((unsigned)a.nwg), dim3(F64G_NW * 64), 0, st, a.B, a.M, a.N, a.K,
+                       a.R, a.L, a.y, a.pack, a.cconst, a.h, a.om, a.os, a.oa, a.pm, a.ps, a.pa, a.pk, a.shift, a.pscr,
+                       a.stamps);
+  } else {
+    hipLaunchKernelGGL((k_est_all_f64g<MP, NP, HM, OP>), dim3((unsigned)a.nwg), dim3(F64G_NW * 64), 0, st, a.B, a.M, a.N, a.K,
+                       a.R, a.L, a.y, a.pack, a.cconst, a.h, a.om, a.os, a.oa, a.pm, a.ps, a.pa, a.pk, a.shift,
+                       a.stamps);
+  }
   return hipGetLastError();
 }
 

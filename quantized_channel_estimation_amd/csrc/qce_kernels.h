@@ -101,6 +101,7 @@ struct QceF64Args {
   double *pm, *ps, *pa;  // scratch for cut tiles: nwg * 2 * tile records
   double* pk = nullptr;   // shifted packed partial B x (2N+2): [s e^{m-shift}, 0, acc e^{m-shift}] (instead of om/os/oa)
   const double* shift = nullptr;  // device pointer: the shared shift M* of the packed partial
+  double* pscr = nullptr;  // two-pass 3M kernel (qce_f64g_scratch_doubles > 0): its softmax-weight scratch
   unsigned long long* stamps = nullptr;  // diagnostic builds (-DQCE_STAMPS): per-wave segment cycles
   int waves = 8;  // workgroup shape where M, N <= 64: 8 waves x 1 column tile (two per SIMD), or 4 x 2 (QCE_F64_WAVES=4)
   int g3 = 0;     // 3M tables / kernel: 1 k_est_all_f64g (padded M, N <= 64; 8 waves x 16 samples), 2 k_est_all_f64h
@@ -115,6 +116,9 @@ hipError_t qce_f64h_launch(const QceF64Args& a, bool out_partial, hipStream_t st
 bool qce_f64g_shape(int MP, int NP);
 int qce_f64g_waves();  // waves per workgroup of k_est_all_f64g (tile = 16 x waves samples; 8 / waves workgroups per CU)
 long long qce_pack_f64g_bytes(int MP, int NP, int has_mean);
+// doubles of scratch the 3M kernel needs for a launch of nwg workgroups (K x 128 per workgroup in its two-pass
+// form, 0 in the single-pass form)
+long long qce_f64g_scratch_doubles(int MP, int NP, int K, long long nwg);
 hipError_t qce_launch_pack_f64g(int K, int M, int N, int MP, int NP, int has_mean, const double2* Linv,
                                 const double2* W, const double2* q0, const double2* bvec, double* pack,
                                 hipStream_t st);

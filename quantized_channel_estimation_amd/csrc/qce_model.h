@@ -96,6 +96,7 @@ struct qce_model {
   DevBuf<char> pack_ws;  // ... and of the two-pass path (qce_wsum_f64.hip)
   int pack64_valid = 0;  // pack64 (the k_lp_f64 table) built without pack32
   DevBuf<double> fp_m, fp_s, fp_a;
+  DevBuf<double> fp_scr;    // two-pass 3M kernel: softmax weights, K x 128 per workgroup of the launch
   DevBuf<double> part_a64;  // FP64 partial accumulator behind the f32 qce_estimate_partial
   DevBuf<double> fp_pack;   // host-I/O staging of qce_estimate_partial_shifted
   DevBuf<double> w64_scr;   // FP64 selection weights (selective modes)
