@@ -307,7 +307,6 @@ QceFftEstArgs fft_args(qce_model* m, const double2* y, long long B) {
   a.pbr = m->f_pbr.p;
   a.pbi = m->f_pbi.p;
   a.cu = m->sched_cus();
-  a.chunk = m->fft_chunk;
   return a;
 }
 

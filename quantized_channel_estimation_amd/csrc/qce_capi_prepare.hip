@@ -237,10 +237,6 @@ static int prepare_impl(qce_model* m, const double* A, int M, double snr_db, dou
     fa.status = m->status.p;
     HIPCHK(qce_launch_fft_prep(fa, st));
     m->fft_mfma = 0;
-    {
-      const char* e = getenv("QCE_FFT_CHUNK");  // read per prepare: the table order and the kernel go together
-      m->fft_chunk = !(e && e[0] == '0');
-    }
     if (qce_fft_mfma_shape(N) && fft_mfma_enabled()) {
       const size_t KpN = (size_t)qce_fft_kpad(K) * N;
       HIPCHK(m->f_pr.ensure(KpN));

@@ -215,8 +215,7 @@ struct QceFftEstArgs {
   // MFMA kernel tables (qce_fft_mfma.hip, storage order, components padded to Kp)
   int Kp;
   const double *pr, *pur, *pui, *pc, *pw, *pbr, *pbi;
-  int cu;     // compute units of the device (persistent grid of k_fft_wave)
-  int chunk;  // N = 128, 256: k_fft_chunk / k_fft_chunk_hm on fragment-order tables (else k_fft_mfma, row-major)
+  int cu;  // compute units of the device (persistent grid of k_fft_wave / k_fft_wreg)
 };
 bool qce_fft_pow2(int v);
 int qce_fft_tile(int N, int K);  // 0: no tile fits (K too large)

@@ -464,8 +464,8 @@ def test_fourier_mfma_kernel_vs_lds_kernel(K, N, blocks, B, n_bits, mean, monkey
 def test_fourier_chunk_kernel(K, N, blocks, B, n_bits, monkeypatch):
     """k_fft_chunk (zero-mean N = 128, 256: components split over the waves for lp / softmax, bins for the
     filter, two barriers per 128-component chunk) and k_fft_wreg (zero-mean N = 64) against the FP64 oracle and
-    the kernels they replace (QCE_FFT_CHUNK=0: bin-split k_fft_mfma, LDS-transform k_fft_wave), 'all' mode and
-    both K-shard partial accumulators."""
+    the LDS-tiled FP64 kernel (qce_fft.hip, QCE_FFT_KERNEL=lds), 'all' mode and both K-shard partial
+    accumulators."""
     _chunk_vs_oracle(K, N, blocks, B, n_bits, False, monkeypatch)
 
 
@@ -487,8 +487,8 @@ def test_fourier_chunk_kernel(K, N, blocks, B, n_bits, monkeypatch):
 def test_fourier_chunk_kernel_means(K, N, blocks, B, n_bits, monkeypatch):
     """k_fft_chunk_hm (N = 128, 256 with means: the mean terms 2 Re(Y^* u) in the log-probabilities and
     sum_k gamma_k b_k in the filter, gmm_cplx_bussgang.py:256-264, :288) and k_fft_wreg<HM> (N = 64 with means)
-    against the FP64 oracle and the kernels they replace (QCE_FFT_CHUNK=0: bin-split k_fft_mfma, LDS-transform
-    k_fft_wave), 'all' mode and both K-shard partial accumulators."""
+    against the FP64 oracle and the LDS-tiled FP64 kernel (qce_fft.hip, QCE_FFT_KERNEL=lds), 'all' mode and both
+    K-shard partial accumulators."""
     _chunk_vs_oracle(K, N, blocks, B, n_bits, True, monkeypatch)
 
 
@@ -507,8 +507,9 @@ def _chunk_vs_oracle(K, N, blocks, B, n_bits, mean, monkeypatch):
         qz = inputs.get_quantizer([5.0], n_bits, "uniform")[5.0]
     y = inputs.get_observation_nbit(h[:, 0, :].astype(complex), 5.0, None, n_bits, qz[0], qz[1], rng=rng)
     out = {}
-    for chunk in ("1", "0"):
-        monkeypatch.setenv("QCE_FFT_CHUNK", chunk)
+    for chunk in ("1", "0"):  # "1": the MFMA kernels (default), "0": the LDS-tiled kernel
+        if chunk == "0":
+            monkeypatch.setenv("QCE_FFT_KERNEL", "lds")
         dm = _lib.DeviceModel(means, covs, w)
         dm.prepare(None, 5.0, float(n_bits))
         assert dm.structure()[2] == 1
@@ -531,12 +532,13 @@ def _chunk_vs_oracle(K, N, blocks, B, n_bits, mean, monkeypatch):
     (128, 64, None, 40013, 3, "lloyd", True),  # cfg3 with means: k_fft_wreg<HM>, one workgroup per CU
 ])
 def test_fourier_wave_kernel_persistent_phases(K, N, blocks, B, n_bits, qtype, mean, monkeypatch):
-    """k_fft_wave (N <= 64) at batches large enough for its main phase: one wave per 16-row tile over
-    whole rounds of the persistent grid, with the next tile's y prefetched behind the current one, then
-    the remainder worked cooperatively by the four waves of a workgroup (zero-mean models).  Small-batch
-    tests reach only the cooperative phase.  One launch (QCE_HOST_PIPELINE=0); rows from the first
-    round, the main/tail boundary and the ragged end are checked against the FP64 oracle, and the first
-    rows against the same rows estimated alone (cooperative phase), to FP64 rounding."""
+    """k_fft_wave (which covers N <= 32) and k_fft_wreg (N = 64, the same persistent schedule) at batches
+    large enough for the main phase: one wave per 16-row tile over whole rounds of the persistent grid,
+    with the next tile's y prefetched behind the current one, then the remainder worked cooperatively by
+    the four waves of a workgroup (zero-mean models).  Small-batch tests reach only the cooperative phase.
+    One launch (QCE_HOST_PIPELINE=0); rows from the first round, the main/tail boundary and the ragged end
+    are checked against the FP64 oracle, and the first rows against the same rows estimated alone
+    (cooperative phase), to FP64 rounding."""
     _gpu_or_skip()
     from oracle import qce_oracle as O
     from quantized_channel_estimation_amd import Gmm_nbit, inputs
