@@ -296,6 +296,35 @@ int qce_rate_mf(const double* h_est, const double* h, int64_t B, int N, const do
 int qce_vae_estimate(int N, int P, const double* x_cplx, double snr_db, double n_bits, const void* logvar,
                      int logvar_is_f32, const double* y, int64_t B, double* h_out, int io, int device, void* stream);
 
+/* The VAE estimator's inference network in one kernel (estimators/vae.py:161-172 and :294-309 forward_nosamp;
+ * csrc/qce_vae_net.hip): features (unitary DFT in FP64, rounded once to float32), the pilot convolutions (kernel
+ * size 1), the encoder up to the latent mean and the decoder, float32 on v_mfma_f32_16x16x4_f32.
+ *
+ * qce_vae_net_create: `widths` (host) holds the convolutions' channel counts (n_pilot_convs + 1 entries, P .. 1), the
+ * encoder's widths (n_layers + 1, 2N .. 2L) and the decoder's (n_layers + 1, L .. N).  `weights` is one flat float32
+ * buffer (host or device memory, as `io` says) in the reference's state-dict order: the convolutions, the encoder's
+ * layers, the decoder's; each layer its weight (out, in) row-major, then its bias.  The library keeps a copy and a
+ * zero-padded repacking.  genie != 0: the network encodes the true channel (one row, always transformed, no
+ * convolutions applied).  Refused before any device call: QCE_ENOTIMPL for N not a power of two in [16, 256], P > 4,
+ * L outside [1, 128], n_layers outside [1, 8], n_pilot_convs > 4, a width above 512; QCE_EARG for inconsistent widths,
+ * P > 1 without convolutions on a non-genie network, n_weights other than the widths imply, a NULL pointer.
+ *
+ * qce_vae_net_forward: net_in (B, P N) c128 observations, pilot-major, or (B, N) true channels for a genie network;
+ * fft_pre == 0 takes [Re | Im] of the observations untransformed.  mu_out (B, L) and logvar_out (B, N) float32 may be
+ * NULL.  With h_out (B, N) c128 non-NULL the call continues on the same stream into the LMMSE of qce_vae_estimate with
+ * y (B, P N), x_cplx, snr_db and n_bits as there (chunks of 65536 rows, two launches per chunk; the log-variances stay
+ * in a scratch of one chunk that the handle owns when logvar_out is NULL), synchronises the stream and returns
+ * QCE_ECHOL as qce_vae_estimate does.  Without h_out and with device buffers the call is asynchronous.  Buffers where
+ * `io` says; `stream` NULL = the null stream of the handle's device.  A handle serves one call at a time.
+ * A row's result does not depend on B or on its place in the batch. */
+typedef struct qce_vae_net qce_vae_net;
+int qce_vae_net_create(int N, int P, int L, int n_layers, int n_pilot_convs, int genie, const int32_t* widths,
+                       const float* weights, int64_t n_weights, int io, int device, qce_vae_net** out);
+int qce_vae_net_forward(qce_vae_net* net, const double* net_in, int fft_pre, int64_t B, float* mu_out, float* logvar_out,
+                        const double* y, const double* x_cplx, double snr_db, double n_bits, double* h_out, int io,
+                        void* stream);
+int qce_vae_net_destroy(qce_vae_net* net);
+
 /* Training side of the VAE estimator (estimators/vae.py:280-281 and :312-365 vae_loss; csrc/qce_vae_train.hip),
  * model-free.  All buffers are device memory (QCE_IO_DEVICE only), all three calls are asynchronous on `stream`
  * (NULL = the null stream of `device`) and leave no status to read; refusals come before any launch.

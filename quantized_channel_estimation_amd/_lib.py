@@ -59,6 +59,12 @@ SIGNATURES = {
                                       ctypes.c_int, ctypes.c_int, _vp]),
     "qce_vae_estimate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, _vp,
                                         ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "qce_vae_net_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(_vp)]),
+    "qce_vae_net_forward": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double,
+                                           ctypes.c_double, _vp, ctypes.c_int, _vp]),
+    "qce_vae_net_destroy": (ctypes.c_int, [_vp]),
     "qce_vae_sample": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
                                       ctypes.c_int, _vp]),
     "qce_vae_sample_bwd": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, _vp]),
@@ -171,16 +177,17 @@ def check(rc):
     raise QceError(f"[qce status {rc}] {msg}")
 
 
-# Every live handle of this process (DeviceModel, Comm, KShard), closed in dependency order by an atexit hook while the
+# Every live handle of this process (DeviceModel, Comm, KShard, a VAE_nbit's packed network), closed in dependency order by an atexit hook while the
 # HIP runtime and RCCL are still fully up: objects Python never collects (reference cycles, module
 # globals) otherwise reach their teardown only through the runtimes' own exit-time destructors.
-_live = {"kshard": weakref.WeakSet(), "comm": weakref.WeakSet(), "model": weakref.WeakSet()}
+_live = {"kshard": weakref.WeakSet(), "comm": weakref.WeakSet(), "model": weakref.WeakSet(),
+         "vae_net": weakref.WeakSet()}
 
 
 def _close_all_at_exit():
     if os.environ.get("QCE_NO_EXIT_CLOSE") == "1":  # diagnostic: leave teardown to the runtimes' destructors
         return
-    for kind in ("kshard", "model", "comm"):
+    for kind in ("kshard", "vae_net", "model", "comm"):
         for obj in list(_live[kind]):
             try:
                 obj.close()

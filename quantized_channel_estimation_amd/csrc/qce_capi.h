@@ -2,6 +2,7 @@
 // check macro and the device guard they all use, then the helpers the qce_capi*.hip units share.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "../../include/qce.h"
 #include "qce_kernels.h"
@@ -28,6 +29,21 @@ struct DeviceGuard {
   ~DeviceGuard() {
     int cur = -1;
     if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+// stream-ordered scratch for the model-free entry points (freed on the same stream)
+struct StreamScratch {
+  hipStream_t st;
+  std::vector<void*> ptrs;
+  explicit StreamScratch(hipStream_t s) : st(s) {}
+  hipError_t get(void** p, size_t bytes) {
+    hipError_t e = hipMallocAsync(p, bytes ? bytes : 1, st);
+    if (e == hipSuccess) ptrs.push_back(*p);
+    return e;
+  }
+  ~StreamScratch() {
+    for (void* p : ptrs) (void)hipFreeAsync(p, st);
   }
 };
 
@@ -59,6 +75,10 @@ QceFftEstArgs fft_args(qce_model* m, const double2* y, long long B);
 int stage_input(qce_model* m, const double* y, long long B, int io, hipStream_t st, const double2** dy);
 // lp (B x K) of the prepared model on the family's log-prob kernel
 int backend_lp(qce_model* m, const double2* x, long long B, double* lp, hipStream_t st);
+
+// qce_capi_free.hip
+// the constants of k_vae for one (snr, n_bits, pilot vector), shared by qce_vae_estimate and qce_vae_net_forward
+int vae_lmmse_args(const char* who, int N, int P, const double* x_cplx, double snr_db, double n_bits, QceVaeArgs* a);
 
 #ifdef QCE_STAMPS
 // qce_capi_debug.hip (diagnostic build): segment cycles of the last FP64 launch

@@ -10,24 +10,35 @@
 #include "qce_capi.h"
 #include "qce_common.h"
 
-namespace {
-
-// stream-ordered scratch for the model-free entry points (freed on the same stream)
-struct StreamScratch {
-  hipStream_t st;
-  std::vector<void*> ptrs;
-  explicit StreamScratch(hipStream_t s) : st(s) {}
-  hipError_t get(void** p, size_t bytes) {
-    hipError_t e = hipMallocAsync(p, bytes ? bytes : 1, st);
-    if (e == hipSuccess) ptrs.push_back(*p);
-    return e;
+// The constants of k_vae for one (snr, n_bits, pilot vector); the caller has checked N and P.
+int vae_lmmse_args(const char* who, int N, int P, const double* x_cplx, double snr_db, double n_bits, QceVaeArgs* a) {
+  a->N = N;
+  a->P = P;
+  a->n_bits = 0;
+  a->delta = 0.0;
+  if (n_bits == 1.0) a->kind = 0;
+  else if (isinf(n_bits) && n_bits > 0) a->kind = 2;
+  else {
+    a->kind = 1;
+    a->n_bits = (int)n_bits;
+    if (!(n_bits >= 2.0) || (double)a->n_bits != n_bits) return qce_set_error(QCE_EARG, std::string(who) + ": n_bits must be an integer >= 1 or inf");
+    if (a->n_bits > QCE_MAX_UNIFORM_BITS)
+      return qce_set_error(QCE_ENOTIMPL, std::string(who) + ": uniform quantisers up to " + std::to_string(QCE_MAX_UNIFORM_BITS) + " bits");
+    a->delta = uniform_step(snr_db, a->n_bits);
   }
-  ~StreamScratch() {
-    for (void* p : ptrs) (void)hipFreeAsync(p, st);
-  }
-};
-
-}  // namespace
+  // the reference builds these constants from torch.tensor(np.pi), a float32 tensor (vae.py:403, :410,
+  // uniform_quantizer.py:79, :86)
+  const float pi_f = (float)M_PI;
+  a->k1 = (double)sqrtf(2.0f / pi_f);
+  a->k2 = (double)((float)a->delta / sqrtf(pi_f));
+  a->k3 = (double)(2.0f / pi_f);
+  a->s2 = pow(10.0, -snr_db / 10.0);
+  for (int p = 0; p < QCE_VAE_MAX_PILOTS; ++p)
+    a->x[p] = p < P ? make_double2(x_cplx[2 * p], x_cplx[2 * p + 1]) : make_double2(0.0, 0.0);
+  a->lv_f32 = 0;
+  a->TS = 0;
+  return QCE_OK;
+}
 
 extern "C" {
 
@@ -629,31 +640,8 @@ int qce_vae_estimate(int N, int P, const double* x_cplx, double snr_db, double n
     return qce_set_error(QCE_ENOTIMPL, "vae_estimate: at most " + std::to_string(QCE_VAE_MAX_PILOTS) + " pilots, got " +
                                   std::to_string(P));
   QceVaeArgs a;
-  a.N = N;
-  a.P = P;
-  a.n_bits = 0;
-  a.delta = 0.0;
-  if (n_bits == 1.0) a.kind = 0;
-  else if (isinf(n_bits) && n_bits > 0) a.kind = 2;
-  else {
-    a.kind = 1;
-    a.n_bits = (int)n_bits;
-    if (!(n_bits >= 2.0) || (double)a.n_bits != n_bits) return qce_set_error(QCE_EARG, "vae_estimate: n_bits must be an integer >= 1 or inf");
-    if (a.n_bits > QCE_MAX_UNIFORM_BITS)
-      return qce_set_error(QCE_ENOTIMPL, "vae_estimate: uniform quantisers up to " + std::to_string(QCE_MAX_UNIFORM_BITS) + " bits");
-    a.delta = uniform_step(snr_db, a.n_bits);
-  }
-  // the reference builds these constants from torch.tensor(np.pi), a float32 tensor (vae.py:403, :410,
-  // uniform_quantizer.py:79, :86)
-  const float pi_f = (float)M_PI;
-  a.k1 = (double)sqrtf(2.0f / pi_f);
-  a.k2 = (double)((float)a.delta / sqrtf(pi_f));
-  a.k3 = (double)(2.0f / pi_f);
-  a.s2 = pow(10.0, -snr_db / 10.0);
-  for (int p = 0; p < QCE_VAE_MAX_PILOTS; ++p)
-    a.x[p] = p < P ? make_double2(x_cplx[2 * p], x_cplx[2 * p + 1]) : make_double2(0.0, 0.0);
+  if (int rc = vae_lmmse_args("vae_estimate", N, P, x_cplx, snr_db, n_bits, &a)) return rc;
   a.lv_f32 = logvar_is_f32 ? 1 : 0;
-  a.TS = 0;
   if (B == 0) return QCE_OK;
   DeviceGuard g(device);
   hipStream_t st = (hipStream_t)stream;

@@ -356,6 +356,39 @@ struct QceVaeArgs {
   int TS;             // samples per workgroup (set by the launcher)
 };
 hipError_t qce_launch_vae(const QceVaeArgs& a, hipStream_t st);
+// The VAE's inference network in one kernel (qce_vae_net.hip; estimators/vae.py:161-172 and :294-309 forward_nosamp):
+// features, pilot convolutions, encoder (mu only) and decoder for a tile of 16 rows per workgroup.
+#define QCE_VAE_NET_MAX_LAYERS 8   // per MLP
+#define QCE_VAE_NET_MAX_CONVS 4
+#define QCE_VAE_NET_MAX_WIDTH 512
+#define QCE_VAE_NET_ROWS 16        // rows per workgroup: the M of v_mfma_f32_16x16x4_f32
+struct QceVaeNetLayer {
+  int ksteps;   // ceil(in / 4): MFMA k-steps (the packed weights are zero beyond in)
+  int ntiles;   // ceil(out / 16): output column tiles (zero weights and bias beyond out)
+  int w_off;    // floats into `packed`: ntiles x ksteps x 64, lane-major per (tile, k-step)
+  int b_off;    // floats into `packed`: 16 ntiles
+  int relu;
+};
+struct QceVaeNetArgs {
+  long long B;
+  int N, P;               // P: rows of N complex values per sample in `in` (1 for a genie network)
+  int L;
+  int dft;                // 1: unitary DFT features, 0: [Re | Im] of the input itself
+  int nconv;              // pilot convolutions (kernel size 1), channels conv_ch[0] = P .. conv_ch[nconv] = 1
+  int conv_ch[QCE_VAE_NET_MAX_CONVS + 1];
+  int conv_off[QCE_VAE_NET_MAX_CONVS];  // floats into `raw`: weight (out, in) row-major, then bias (out)
+  int nenc, nlayers;      // layers [0, nenc) are the encoder's (the last keeps its first L outputs), the rest the decoder's
+  QceVaeNetLayer layer[2 * QCE_VAE_NET_MAX_LAYERS];
+  int stride;             // floats per row of an activation buffer: >= every padded width, = 4 mod 64
+  int spp;                // samples transformed per pass (spp P (N + 1) complex values of staging)
+  const float* raw;       // the caller's flat weights (the convolutions are read from here)
+  const float* packed;
+  const double2* in;      // B x (P N)
+  float* mu;              // B x L, or nullptr
+  float* lv;              // B x N
+};
+size_t qce_vae_net_lds(const QceVaeNetArgs& a);
+hipError_t qce_launch_vae_net(const QceVaeNetArgs& a, hipStream_t st);
 // VAE training: reparameterisation and the fused row ELBO with its gradient (qce_vae_train.hip; estimators/vae.py:280-281,
 // :312-365)
 #define QCE_VAE_MAX_LATENT 128

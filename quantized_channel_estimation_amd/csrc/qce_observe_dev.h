@@ -79,4 +79,38 @@ QCE_DEV double2 observe_one(double2 v, double2 w, double s, int noise, int kind,
   return v;
 }
 
+QCE_DEV int r_bitrev(int j, int lg) { return (int)(__brev((unsigned)j) >> (32 - lg)); }
+
+// The feature transform of qce_observe_rows.hip and qce_vae_net.hip (one definition: their features agree to the bit).
+// In-place radix-2 DIT transform (unnormalised, e^{-}) of every row of the tile; tw[t] = e^{-2 pi i t / N}, t < N / 2.
+// Starts from rows complete in LDS behind a barrier and ends with a barrier.
+template <int THREADS>
+QCE_DEV void r_fft_rows(double2* T, int G, int N, int lgN, const double2* tw) {
+  const int RS = N + 1;
+  for (int e = threadIdx.x; e < G * N; e += THREADS) {
+    const int r = e >> lgN, j = e & (N - 1), rv = r_bitrev(j, lgN);
+    if (j < rv) {
+      double2* row = T + r * RS;
+      const double2 u = row[j];
+      row[j] = row[rv];
+      row[rv] = u;
+    }
+  }
+  __syncthreads();
+  const int hN = N >> 1;
+  for (int lgl = 1; lgl <= lgN; ++lgl) {
+    const int half = 1 << (lgl - 1), wshift = lgN - lgl;
+    for (int e = threadIdx.x; e < G * hN; e += THREADS) {
+      const int r = e >> (lgN - 1), q = e & (hN - 1);
+      const int blk = q >> (lgl - 1), t = q & (half - 1);
+      const int j0 = (blk << lgl) + t;
+      double2* row = T + r * RS;
+      const double2 u = row[j0], v = cmul(row[j0 + half], tw[t << wshift]);
+      row[j0] = cadd(u, v);
+      row[j0 + half] = csub(u, v);
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace qce_obs

@@ -66,38 +66,6 @@ QCE_DEV double2 pilot_mul(double2 x, double2 h) {
   return make_double2(x.x * h.x - x.y * h.y, x.x * h.y + x.y * h.x);
 }
 
-QCE_DEV int r_bitrev(int j, int lg) { return (int)(__brev((unsigned)j) >> (32 - lg)); }
-
-// In-place radix-2 DIT transform (unnormalised, e^{-}) of every row of the tile; tw[t] = e^{-2 pi i t / N}, t < N / 2.
-// Starts from rows complete in LDS behind a barrier and ends with a barrier.
-QCE_DEV void r_fft_rows(double2* T, int G, int N, int lgN, const double2* tw) {
-  const int RS = N + 1;
-  for (int e = threadIdx.x; e < G * N; e += ROWS_THREADS) {
-    const int r = e >> lgN, j = e & (N - 1), rv = r_bitrev(j, lgN);
-    if (j < rv) {
-      double2* row = T + r * RS;
-      const double2 u = row[j];
-      row[j] = row[rv];
-      row[rv] = u;
-    }
-  }
-  __syncthreads();
-  const int hN = N >> 1;
-  for (int lgl = 1; lgl <= lgN; ++lgl) {
-    const int half = 1 << (lgl - 1), wshift = lgN - lgl;
-    for (int e = threadIdx.x; e < G * hN; e += ROWS_THREADS) {
-      const int r = e >> (lgN - 1), q = e & (hN - 1);
-      const int blk = q >> (lgl - 1), t = q & (half - 1);
-      const int j0 = (blk << lgl) + t;
-      double2* row = T + r * RS;
-      const double2 u = row[j0], v = cmul(row[j0 + half], tw[t << wshift]);
-      row[j0] = cadd(u, v);
-      row[j0 + half] = csub(u, v);
-    }
-    __syncthreads();
-  }
-}
-
 // NOISE: 0 none, 1 supplied, 2 generated.  FEAT: 0 y output, 1 features (a.out 1 raw, 2 DFT).
 template <int NOISE, int FEAT>
 __global__ __launch_bounds__(ROWS_THREADS) void k_observe_rows(QceObserveRowsArgs a, RowsPlan pl) {
@@ -195,7 +163,7 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_observe_rows(QceObserveRowsArg
 
     if (FEAT) {
       __syncthreads();
-      if (dft) r_fft_rows(T, G, N, pl.lgSL, tw);
+      if (dft) r_fft_rows<ROWS_THREADS>(T, G, N, pl.lgSL, tw);
       const double rs = dft ? 1.0 / sqrt((double)N) : 1.0;
       // row g of the output: 2N floats [Re | Im]; four consecutive floats per thread
       const int q4row = N >> 1;  // float4 groups per row

@@ -4,7 +4,10 @@ Evaluation.  ``lmmse_from_decoder`` is the hot path: the reference's ``convert_d
 zeromean=True) followed by ``lmmse`` (:368-369), computed by libqce.so in the Fourier domain (``qce_vae_estimate``,
 csrc/qce_vae.hip).  ``VAE_nbit`` wraps it with the reference's input preparation (:161-172) and the encoder / decoder
 forward of ``DNN_VAE.forward_nosamp`` (:294-309), written as torch.nn.functional calls in float32 on the device (the
-reference's precision; this part is plumbing).
+reference's precision; this part is plumbing).  ``fused=True`` (``estimate_from_y``, ``eval``) and ``forward_fused``
+run the same network inside libqce.so instead (``qce_vae_net_forward``, csrc/qce_vae_net.hip): features, pilot
+convolutions, encoder and decoder in one kernel, then the LMMSE kernel on the same stream, two launches per chunk and
+no torch op.  The default stays the torch path.
 
 Training.  ``VAE_nbit.train`` is the reference's loop (:15-154) on the device.  The layers stay torch.nn.functional
 calls under autograd; what lies between and around them is libqce.so (csrc/qce_vae_train.hip): ``reparameterize``
@@ -309,8 +312,46 @@ class VAE_nbit:
         if params["vae_mode"] != "genie" and int(params["n_pilots"]) > 1 and not int(params.get("n_pilot_convs", 0)):
             raise NotImplementedError("several pilots need n_pilot_convs >= 1 (the reference's encoder takes one row)")
         self._w = None
+        self._net = None  # the packed handle of the fused forward (qce_vae_net), built on first use
+
+    def __del__(self):
+        try:
+            self._drop_net()
+        except Exception:  # interpreter teardown
+            pass
 
     # ------------------------------------------------------------------ weights
+    def _drop_net(self):
+        """Destroy the packed handle: the weights it was built from are being replaced (or the object goes)."""
+        net, self._net = getattr(self, "_net", None), None
+        if net is not None:
+            _lib.load().qce_vae_net_destroy(net)
+
+    def _net_handle(self):
+        """The library's handle for the current weights (``qce_vae_net_create``), cached until they change."""
+        if self._w is None:
+            raise RuntimeError("no weights: call load_state_dict, from_checkpoint or train first")
+        if self._net is not None:
+            return self._net
+        import ctypes
+        import torch
+        p = self.params
+        N, P, L, nl = (int(p[k]) for k in ("n_antennas", "n_pilots", "latent_dim", "n_layers"))
+        npc = int(p.get("n_pilot_convs", 0))
+        widths = np.concatenate([np.linspace(P, 1, npc + 1, dtype=int), np.linspace(2 * N, 2 * L, nl + 1, dtype=int),
+                                 np.linspace(L, N, nl + 1, dtype=int)]).astype(np.int32)
+        flat = torch.cat([self._w[name].detach().reshape(-1) for name in layer_shapes(p)]).contiguous()
+        out = ctypes.c_void_p()
+        _lib.check(_lib.load().qce_vae_net_create(N, P, L, nl, npc, int(p["vae_mode"] == "genie"), _lib.ptr(widths),
+                                                  _lib.ptr(flat), flat.numel(), _lib.IO_DEVICE, flat.device.index or 0,
+                                                  ctypes.byref(out)))
+        self._net = out
+        _lib._live["vae_net"].add(self)  # closed at exit while the HIP runtime is still up
+        return out
+
+    def close(self):
+        """Free the library's handle of the fused forward (it is rebuilt on the next fused call)."""
+        self._drop_net()
     def _device(self):
         import torch
         d = self.params.get("device", 0)
@@ -335,6 +376,7 @@ class VAE_nbit:
             if tuple(t.shape) != shape:
                 raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
             w[name] = t
+        self._drop_net()
         self._w = w
         return self
 
@@ -458,6 +500,7 @@ class VAE_nbit:
             bound = 1.0 / np.sqrt(fan_in)
             t = (torch.rand(shape, generator=gen, device=dev, dtype=torch.float32) * 2 - 1) * bound
             w[name] = t.requires_grad_(True)
+        self._drop_net()
         self._w = w
 
     def _train_data(self, h_dev, snr_list, seed, row_offset):
@@ -548,6 +591,7 @@ class VAE_nbit:
                         "loss_all": losses_all, "epoch": epoch, "params": p}, file_vae)
         for v in self._w.values():
             v.requires_grad_(False)
+        self._drop_net()  # the optimiser has updated the weights in place
         return losses_all, losses_all_test
 
     def _estimate(self, y, snr, h):
@@ -565,9 +609,85 @@ class VAE_nbit:
             lv = self.forward_nosamp(self._inputs(y_t, h, B))
         return lmmse_from_decoder(y_t, lv, snr, p.get("A"), p["n_bits"], p.get("quantizer_type", "uniform"), True)
 
-    def estimate_from_y(self, y, snr, h=None):
+    # ------------------------------------------------------------------ fused forward
+    def _net_call(self, y, h, snr=None, return_mu=False, want_lv=True):
+        """One ``qce_vae_net_forward``: (lv, mu, h_hat), each None when not asked for (h_hat with ``snr``).  numpy
+        arrays go through the library's host staging, CUDA tensors are used in place on the current stream."""
+        p = self.params
+        if not p.get("zeromean", True):
+            raise ValueError(ZEROMEAN_MESSAGE)
+        N, P, L = int(p["n_antennas"]), int(p["n_pilots"]), int(p["latent_dim"])
+        genie = p["vae_mode"] == "genie"
+        x, nb, other = None, 1.0, False
+        if snr is not None:  # the refusals of the unfused path, before anything is uploaded or launched
+            x = pilot_vector(p.get("A"), N)
+            nb = _nbits(p["n_bits"])
+            qt = p.get("quantizer_type", "uniform")
+            if nb != 1.0 and not np.isinf(nb) and qt == "lloyd":
+                raise TypeError(LLOYD_MESSAGE)
+            if x.size != P:
+                raise ValueError(f"A has {x.size} pilots, n_pilots is {P}")
+            other = nb != 1.0 and not np.isinf(nb) and qt != "uniform"  # the gain stays 0 (:421-426): h = 0
+        if genie and h is None:
+            raise ValueError("vae_mode 'genie' encodes the true channel: pass h")
+        tensors = _is_tensor(y) or (genie and _is_tensor(h))
+        if tensors:
+            import torch
+            dev = y.device if _is_tensor(y) else h.device
+            if dev.type != "cuda":
+                dev = self._device()
+
+            def prep(v, cols):
+                v = torch.as_tensor(v, device=dev).to(torch.complex128)
+                return v.reshape(v.numel() // cols, cols).contiguous()
+
+            def new(shape, dtype):
+                return torch.empty(shape, dtype={"f": torch.float32, "c": torch.complex128}[dtype], device=dev)
+            io, stream = _lib.IO_DEVICE, torch.cuda.current_stream(dev).cuda_stream
+        else:
+            def prep(v, cols):
+                v = np.ascontiguousarray(v, dtype=np.complex128)
+                return v.reshape(v.size // cols, cols)
+
+            def new(shape, dtype):
+                return np.empty(shape, dtype={"f": np.float32, "c": np.complex128}[dtype])
+            io, stream = _lib.IO_HOST, None
+        net = self._net_handle()
+        y_c = None if (genie and y is None) else prep(y, P * N)
+        src = prep(h, N) if genie else y_c
+        B = int(src.shape[0])
+        if y_c is not None and int(y_c.shape[0]) != B:
+            raise ValueError(f"y has {int(y_c.shape[0])} rows, h has {B}")
+        lv = new((B, N), "f") if want_lv else None
+        mu = new((B, L), "f") if return_mu else None
+        hh = None
+        if snr is not None:
+            hh = new((B, N), "c")
+            if other or not B:
+                hh[...] = 0
+        run_lmmse = snr is not None and not other
+        if B and (want_lv or return_mu or run_lmmse):
+            _lib.check(_lib.load().qce_vae_net_forward(
+                net, _lib.ptr(src), int(bool(p.get("fft_pre", True))), B, _lib.ptr(mu) if return_mu else None,
+                _lib.ptr(lv) if want_lv else None, _lib.ptr(y_c) if run_lmmse else None,
+                _lib.ptr(x) if run_lmmse else None, float(snr) if run_lmmse else 0.0, nb,
+                _lib.ptr(hh) if run_lmmse else None, io, stream))
+        return lv, mu, hh
+
+    def forward_fused(self, y, h=None, *, return_mu=False):
+        """Decoder log-variances (B, N) float32 from the raw observations y (B, P N) complex (``h`` (B, N): the true
+        channels, which a 'genie' network encodes instead), computed by one kernel of libqce.so (``k_vae_net``);
+        ``return_mu``: (lv, mu (B, L) float32).  numpy in, numpy out; CUDA tensor in, tensor out (asynchronous on
+        the current stream)."""
+        lv, mu, _ = self._net_call(y, h, return_mu=return_mu)
+        return (lv, mu) if return_mu else lv
+
+    def estimate_from_y(self, y, snr, h=None, *, fused=False):
         """Channel estimates (B, N) for observations y (B, P N); any B >= 1.  ``h``: the true channels, needed by
-        vae_mode 'genie' only.  numpy in, numpy out; CUDA tensor in, tensor out."""
+        vae_mode 'genie' only.  numpy in, numpy out; CUDA tensor in, tensor out.  ``fused``: the network runs
+        inside libqce.so (``qce_vae_net_forward``), two launches per chunk instead of the torch calls."""
+        if fused:
+            return self._net_call(y, h, snr=snr, want_lv=False)[2]
         hh = self._estimate(y, snr, h)
         return hh if _is_tensor(y) else hh.cpu().numpy()
 
@@ -600,17 +720,24 @@ class VAE_nbit:
             np.fill_diagonal(Cr, _rate.quantized_variance(d, q[0], q[1]))
         return g, Cr - (g[:, None] * cov) * g[None, :]
 
-    def eval(self, h_eval, y_eval, snr, h_train):
+    def eval(self, h_eval, y_eval, snr, h_train, *, fused=False):
         """(mse, rate, params) as the reference's eval (:157-228): MSE = sum |h_hat - h|^2 / h.size on the device,
         rate = the statistical lower bound with the global Bussgang pair of the training channels' sample covariance
-        (g = h_hat / ||h_hat||^2; torch.var's n - 1 normalisation of the inner products)."""
+        (g = h_hat / ||h_hat||^2; torch.var's n - 1 normalisation of the inner products).  ``fused``: the estimates
+        come from ``estimate_from_y(..., fused=True)``."""
         p = self.params
         h_eval = np.asarray(h_eval)
         B = h_eval.shape[0]
         if p["vae_mode"] != "genie" and B % EVAL_BATCH == 1:
             raise IndexError(BATCH1_MESSAGE)
-        hh = self._estimate(y_eval, snr, h_eval)
         import torch
+        if fused:
+            dev = self._device()
+            hh = self._net_call(torch.as_tensor(y_eval, device=dev),
+                                torch.as_tensor(h_eval, device=dev) if p["vae_mode"] == "genie" else None,
+                                snr=snr, want_lv=False)[2]
+        else:
+            hh = self._estimate(y_eval, snr, h_eval)
         h_t = torch.as_tensor(h_eval, device=hh.device).to(torch.complex128)
         mse = float(observe.sq_error(hh, h_t)) / h_eval.size
         if not p.get("eval_rate", False):
@@ -621,3 +748,9 @@ class VAE_nbit:
         _, t = _rate.statistical_rate_bound(hh, h_t, g, Cq, return_terms=True)
         den1 = t["den1"] * B / (B - 1) if B > 1 else float("nan")  # torch.var is unbiased (:222)
         return mse, float(np.log2(1 + t["num"] / (den1 + t["den2"]))), self.params
+
+
+def forward_fused(model, y, h=None, *, return_mu=False):
+    """``model.forward_fused(y, h, return_mu=...)`` for a ``VAE_nbit`` with weights: the decoder log-variances (B, N)
+    float32 of the raw observations, from one kernel of libqce.so (csrc/qce_vae_net.hip)."""
+    return model.forward_fused(y, h, return_mu=return_mu)
