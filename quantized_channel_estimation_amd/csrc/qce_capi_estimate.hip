@@ -209,7 +209,7 @@ int run_h2(qce_model* m, const double2* dy, long long B, double2* h, double* om,
   HIPCHK(m->sp_m.ensure((size_t)nwg * 2 * 256));
   HIPCHK(m->sp_s.ensure((size_t)nwg * 2 * 256));
   HIPCHK(m->sp_a.ensure((size_t)nwg * 2 * 256 * 2 * m->N));
-  HIPCHK(m->yflag.ensure(1));
+  HIPCHK(m->yflag.ensure(2));  // inexact flag, largest exponent (k_y_exact)
   a.yflag = m->yflag.p;
   a.pm = m->sp_m.p;
   a.ps = m->sp_s.p;
@@ -240,7 +240,7 @@ int run_h2x(qce_model* m, const double2* dy, long long B, double2* h, double* om
   QceH2XArgs a;
   set_shape(a, m, B);
   a.y_scale = m->y_scale;
-  HIPCHK(m->yflag.ensure(1));
+  HIPCHK(m->yflag.ensure(2));  // inexact flag, largest exponent (k_y_exact)
   a.yflag = m->yflag.p;
   a.y = dy;
   a.pack = m->pack16.p;

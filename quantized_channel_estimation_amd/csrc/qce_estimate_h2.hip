@@ -10,9 +10,14 @@
 //    uniform b-bit: y*2/delta = odd integers <= 255), so a*y = a_hi*y + a_lo*y is two
 //    v_mfma_f32_32x32x16_f16 with fp32 accumulation — fp32-class results at 1/8 of the fp32-MFMA
 //    cycles.  Observations that are not exact (Lloyd-Max labels, n_bits = inf, or any unquantised
-//    input) are split too (y = y_hi + y_lo) and the wave takes a three-product path
-//    (a_hi y_hi + a_lo y_hi + a_hi y_lo); the choice is made per workgroup tile (any inexact
-//    sample), so no input can silently lose precision;
+//    input) are split too and the wave takes a three-product path (a_hi y_hi + a_lo y_hi +
+//    a_hi y_lo).  The choice is made per batch (k_y_exact: any inexact sample), and the same pass
+//    finds the batch's largest exponent: the inexact path scales y by the power of two g that puts
+//    its largest entry into [2^13, 2^14) before splitting y g = y_hi + y_lo (y_split_exp), so the
+//    split carries 22 significant bits relative to that entry at any input amplitude.  (Without
+//    g the residual y_lo of |y| <~ 1e-2 fell into fp16 subnormals: 2e-5 relative error at |y| ~
+//    1e-3, 4e-4 at 1e-4.)  g is a power of two between 2^-14 and 2^15 (it replaces the 1 of
+//    [y; 1] as an fp16 number); below |y| ~ 2^-18 the split loses bits again;
 //  * one 512-thread workgroup = 8 waves x 32 samples shares each component's tables through LDS:
 //    the Linv part (GL) and the W part (GW) have their own LDS slot and are streamed by
 //    global_load_lds (16 B per lane) one phase ahead of the MFMAs that read them;
@@ -296,7 +301,9 @@ QCE_DEV void gw_phase_x(const char* sw, const f16x8* yh, const float* sk, float 
 template <int MP, int NP, bool HM, bool Y2>
 QCE_DEV void h2_kloop(int k0, int k1, const char* __restrict__ pack, long long cstride, const float* __restrict__ sinv,
                       const double* __restrict__ cconst, const f16x8* yh, const f16x8* yl, char* lds,
-                      f32x16 (&out)[H2Geom<MP, NP, HM>::NSW], double& m, double& ssum, int wave, int lane) {
+                      f32x16 (&out)[H2Geom<MP, NP, HM>::NSW], double& m, double& ssum, float ginv, int wave,
+                      int lane) {
+  // ginv: 1 / g of the inexact path's observation scale (y_split_exp)
   using G = H2Geom<MP, NP, HM>;
   char* slotL = lds;
   char* slotW = lds + G::GL_BYTES;
@@ -310,8 +317,10 @@ QCE_DEV void h2_kloop(int k0, int k1, const char* __restrict__ pack, long long c
     const float* sk = cs.s;
     double quad = gl_phase<MP, NP, HM, Y2>(slotL, yh, yl, sk, lane);
     quad += __shfl_xor(quad, 32);
+    if constexpr (Y2) quad *= (double)ginv * (double)ginv;  // u was computed from y g
     float alpha, p;
     softmax_step(cs.c - quad, m, ssum, alpha, p);
+    if constexpr (Y2) p *= ginv;  // and so is Z: the filter rows take p / g (after the sum took p)
     wait_vm<0>();  // GW_k landed
     raw_barrier();  // and every wave is done with slot L
     if (k + 1 < k1) stage<G::GL_BYTES>(pack + (long long)(k + 1) * cstride, slotL, wave, lane);
@@ -429,6 +438,13 @@ __global__ __launch_bounds__(512) void k_est_all_h2(long long B, int M, int N, i
   const long long item1 = (item0 + L < (tiles - tail0) * K) ? item0 + L : (tiles - tail0) * K;
   const long long t_first = tail0 + (L > 0 ? item0 / K : 0);
   const long long nseg = (long long)R + (item1 > item0 ? (item1 - 1) / K - item0 / K + 1 : 0);
+  float gf = 1.0f, ginv = 1.0f;  // the inexact path's observation scale g = 2^e and its inverse
+  if constexpr (!EXACT) {
+    const int ge = y_split_exp(yflag);
+    gf = pow2f_uniform(ge);
+    ginv = pow2f_uniform(-ge);
+    y_scale *= (double)gf;
+  }
   for (long long seg = 0; seg < nseg; ++seg) {
     long long t;
     int klo, khi;
@@ -467,7 +483,7 @@ __global__ __launch_bounds__(512) void k_est_all_h2(long long B, int M, int N, i
     if (HM) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) yh[G::KS][e] = (_Float16)0.0f;
-      if (hh == 0) yh[G::KS][0] = (_Float16)1.0f;  // the [y; 1] augmentation column
+      if (hh == 0) yh[G::KS][0] = (_Float16)gf;  // the [y; 1] augmentation column (inexact path: [y g; g])
     }
     f32x16 out[G::NSW];
 #pragma unroll
@@ -478,7 +494,8 @@ __global__ __launch_bounds__(512) void k_est_all_h2(long long B, int M, int N, i
     if constexpr (DEEP)
       h2_kloop_deep<false>(klo, khi, pack, cstride, sinv, cconst, yh, yl, lds, out, m, ssum, wave, lane);
     else
-      h2_kloop<MP, NP, HM, !EXACT>(klo, khi, pack, cstride, sinv, cconst, yh, yl, lds, out, m, ssum, wave, lane);
+      h2_kloop<MP, NP, HM, !EXACT>(klo, khi, pack, cstride, sinv, cconst, yh, yl, lds, out, m, ssum, ginv, wave,
+                                   lane);
     if (!valid) continue;
     if (klo == 0 && khi == K) {
       write_final(h, om, os, oa, sample, N, hh, G::NSW, out, m, ssum, OUT_PARTIAL);
@@ -753,16 +770,40 @@ __global__ __launch_bounds__(256) void k_est_all_h2w(long long B, int M, int N, 
   }
 }
 
-// *flag |= (some y * y_scale is not exactly representable in fp16)
+// flag[0] |= (some y * y_scale is not exactly representable in fp16); flag[1] = the largest biased FP64 exponent of
+// |y * y_scale| over the batch, from which the inexact path takes its observation scale (y_split_exp)
 __global__ __launch_bounds__(256) void k_y_exact(long long n, const double* __restrict__ y, double y_scale,
                                                  int* __restrict__ flag) {
   bool bad = false;
+  int eb = 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const double v = y[i] * y_scale;
     const _Float16 hv = (_Float16)v;
     bad |= (_Float16)(v - (double)hv) != (_Float16)0.0f;
+    const int e = (__double2hiint(v) >> 20) & 0x7ff;
+    eb = e > eb ? e : eb;
   }
-  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int other = __shfl_xor(eb, o);
+    eb = other > eb ? other : eb;
+  }
+  // one pair of atomics per workgroup at most, and none where the flag words already say as much: the maximum is
+  // over every entry (an exact one may be the largest), but quantiser outputs have a handful of exponents
+  __shared__ int s_eb[4], s_bad[4];
+  const bool wave_bad = __ballot(bad) != 0ull;
+  if ((threadIdx.x & 63) == 0) {
+    s_eb[threadIdx.x >> 6] = eb;
+    s_bad[threadIdx.x >> 6] = wave_bad ? 1 : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int i = 1; i < 4; ++i) {
+    eb = s_eb[i] > eb ? s_eb[i] : eb;
+    s_bad[0] |= s_bad[i];
+  }
+  if (s_bad[0] && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(flag, 1);
+  if (__hip_atomic_load(flag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < eb) atomicMax(flag + 1, eb);
 }
 
 hipError_t qce_launch_y_exact(long long n, const double* y, double y_scale, int* flag, hipStream_t st) {
@@ -945,7 +986,7 @@ static hipError_t launch_h2_t(const QceH2Args& a, bool out_partial, hipStream_t 
 
 hipError_t qce_launch_est_h2(const QceH2Args& a, bool out_partial, hipStream_t st) {
   const bool hm = a.has_mean != 0;
-  hipError_t e = hipMemsetAsync(a.yflag, 0, sizeof(int), st);
+  hipError_t e = hipMemsetAsync(a.yflag, 0, 2 * sizeof(int), st);
   if (e != hipSuccess) return e;
   if ((e = qce_launch_y_exact(a.B * a.M * 2, reinterpret_cast<const double*>(a.y), a.y_scale, a.yflag, st)) !=
       hipSuccess)

@@ -67,7 +67,7 @@ int qce_h2x_row_chunks(int MP, int NP) { return ((2 * NP) / 32) / x_rsw(MP, NP, 
 
 hipError_t qce_launch_est_h2x(const QceH2XArgs& a, int ksplit, bool out_partial, hipStream_t st) {
   const bool hm = a.has_mean != 0;
-  hipError_t e = hipMemsetAsync(a.yflag, 0, sizeof(int), st);
+  hipError_t e = hipMemsetAsync(a.yflag, 0, 2 * sizeof(int), st);
   if (e != hipSuccess) return e;
   if ((e = qce_launch_y_exact(a.B * a.M * 2, reinterpret_cast<const double*>(a.y), a.y_scale, a.yflag, st)) !=
       hipSuccess)

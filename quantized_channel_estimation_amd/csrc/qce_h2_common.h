@@ -53,6 +53,22 @@ struct CompScalars {
   }
 };
 
+// Observation scale of the inexact (three-product) path.  k_y_exact leaves the largest biased FP64 exponent of
+// |y * y_scale| over the batch in yflag[1] (0: nothing above the FP64 subnormals).  The batch is multiplied by
+// g = 2^e, e = 14 - frexp exponent of that maximum, so that its largest entry lies in [2^13, 2^14) -- the range the
+// table slices use -- before y g = y_hi + y_lo is split: y_lo then stays in fp16's normal range for every entry
+// within 2^-14 of the maximum and the pair carries 22 significant bits relative to it, whatever the amplitude of
+// the input.  The constant of [y; 1] becomes g, an fp16 number, hence e in [-14, 15]; 1 / g^2 is taken out of the
+// quad form and 1 / g out of the filter weight (powers of two: no rounding anywhere).
+QCE_DEV int y_split_exp(const int* __restrict__ yflag) {
+  const int eb = yflag[1];
+  if (eb == 0) return 0;
+  const int e = 1036 - eb;  // frexp exponent = eb - 1022
+  return e < -14 ? -14 : (e > 15 ? 15 : e);
+}
+// 2^e for e in [-14, 15], assembled in a scalar register (wave-uniform: costs no vector register)
+QCE_DEV float pow2f_uniform(int e) { return __int_as_float(__builtin_amdgcn_readfirstlane((127 + e) << 23)); }
+
 template <int OFF>
 QCE_DEV void ds_rd(f16x8& v, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));

@@ -5,7 +5,9 @@
 // :331-332, :388-435, :632-656): per component k the whitened residual u = E(Linv_k)[y;1] (GL,
 // lower-triangular 32x16 tiles skipped), lp = c_k - |u|^2, an online softmax over k, and
 // Z = E(W_k)[y;1] (GW) folded into the accumulator; FP16 two-term split tables on
-// v_mfma_f32_32x32x16_f16, fp32 accumulation, FP64 quad form / softmax state.
+// v_mfma_f32_32x32x16_f16, fp32 accumulation, FP64 quad form / softmax state.  Observations that are
+// not exact in fp16 take the three-product instance (EXACT = false), which scales the batch by the
+// power of two g of y_split_exp (qce_h2_common.h) before the y_hi + y_lo split, as k_est_all_h2 does.
 //
 // What changes with size: a component's tables no longer fit in LDS (MP = NP = 256: 544 KB GL +
 // 1 MB GW), so they are streamed through a ring of X_NSLOT chunks of X_CH k-steps (16 KB each) by
@@ -114,11 +116,18 @@ __global__ __launch_bounds__(256, 1) void k_est_all_h2x(long long B, int M, int 
 
   // Y^T fragments: k-step s covers real features 16s + 8hh + e = complex 8s + 4hh + e/2.  Loads are
   // clamped in-bounds and masked (no per-element branches); double -> fp16 goes through fp32 (the
-  // hi/lo split stays exact to ~22 bits, and exact observations are small integers anyway).
+  // hi/lo split stays exact to ~22 bits, and exact observations are small integers anyway).  Inexact observations
+  // are first scaled by g = 2^e taken from the batch (y_split_exp); 1 / g is taken out of quad and the filter weight.
   f16x8 yh[KS + X::HMI], yl[EXACT ? 1 : KS];
+  float gf = 1.0f, ginv = 1.0f;
+  if constexpr (!EXACT) {
+    const int ge = y_split_exp(yflag);
+    gf = pow2f_uniform(ge);
+    ginv = pow2f_uniform(-ge);
+  }
   {
     const long long srow = valid ? sample : B - 1;
-    const float ys = (float)y_scale;
+    const float ys = EXACT ? (float)y_scale : (float)y_scale * gf;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
 #pragma unroll
@@ -141,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void k_est_all_h2x(long long B, int M, int 
   if (HM) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) yh[KS][e] = (_Float16)0.0f;
-    if (hh == 0) yh[KS][0] = (_Float16)1.0f;  // the [y; 1] augmentation column
+    if (hh == 0) yh[KS][0] = (_Float16)gf;  // the [y; 1] augmentation column (inexact path: [y g; g])
   }
   f32x16 out[RSW];
 #pragma unroll
@@ -223,7 +232,9 @@ __global__ __launch_bounds__(256, 1) void k_est_all_h2x(long long B, int M, int 
               }
               if constexpr (v == NVL - 1) {  // GL done: online softmax step
                 quad += __shfl_xor(quad, 32);
+                if constexpr (!EXACT) quad *= (double)ginv * (double)ginv;  // u was computed from y g
                 softmax_step(cur.c - quad, m, ssum, alpha, p);
+                if constexpr (!EXACT) p *= ginv;  // and so is Z: the filter rows take p / g (after the sum took p)
               }
             } else {  // GW step of slice w0 + rr
               constexpr int wv = v - NVL, rr = wv / SPS, s = wv % SPS;

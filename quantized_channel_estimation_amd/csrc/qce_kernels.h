@@ -67,7 +67,8 @@ struct QceH2Args {
   int R;        // data-parallel rounds of whole tiles
   long long L;  // stream-K tail: work items (tile, component) per workgroup
   double y_scale;
-  int* yflag;  // device int: set when some observation is not exact in fp16 (k_y_exact)
+  int* yflag;  // two device ints (k_y_exact): [0] set when some observation is not exact in fp16, [1] the largest
+               // biased FP64 exponent of |y * y_scale| (the inexact path's observation scale)
   const double2* y;
   const char* pack;
   long long cstride;  // bytes per component
@@ -156,7 +157,8 @@ hipError_t qce_launch_wsum(const QceWsumArgs& a, hipStream_t st);
 
 hipError_t qce_launch_f32_to_f64(const float* a, double* b, long long n, hipStream_t st);
 
-// *flag |= (some y * y_scale is not exactly representable in fp16); n = doubles in y
+// flag[0] |= (some y * y_scale is not exactly representable in fp16), flag[1] = largest biased FP64 exponent of
+// |y * y_scale| (atomicMax; the caller zeroes both); n = doubles in y
 hipError_t qce_launch_y_exact(long long n, const double* y, double y_scale, int* flag, hipStream_t st);
 
 // chunk-streamed FP16 split kernel for padded M or N of 128 / 256 (qce_estimate_h2x.hip)

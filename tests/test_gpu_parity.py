@@ -211,10 +211,11 @@ def test_device_io_torch():
 
 
 @pytest.mark.parametrize("env", [{}, {"QCE_WORKGROUPS": "1"}, {"QCE_WORKGROUPS": "7"}, {"QCE_WORKGROUPS": "100"},
-                                 {"QCE_WORKGROUPS": "5000"}, {"QCE_KERNEL": "f32"}, {"QCE_H2_NARROW": "1"}])
+                                 {"QCE_WORKGROUPS": "5000"}, {"QCE_KERNEL": "f32"}])
 def test_all_mode_kernel_variants_vs_oracle(env, monkeypatch):
-    """FP16 two-term split kernel (default) under different stream-K cuts (1 workgroup, uneven
-    cuts, more workgroups than items), and the FP32-MFMA kernel, all agree with the FP64 oracle."""
+    """The default FP64 kernel under different stream-K cuts (1 workgroup, uneven cuts, more workgroups than
+    items), and the FP32-MFMA kernel (QCE_KERNEL=f32 moves the model into the fast family), all agree with the FP64
+    oracle.  The fp16 two-term split kernels under the same cuts: tests/test_gpu_fast.py."""
     _gpu_or_skip()
     from oracle import qce_oracle as O
     from quantized_channel_estimation_amd import Gmm_nbit
@@ -230,8 +231,9 @@ def test_all_mode_kernel_variants_vs_oracle(env, monkeypatch):
 
 @pytest.mark.parametrize("n_bits,snr", [(1, -10.0), (1, 20.0), (2, 5.0), (np.inf, 10.0)])
 def test_inexact_observations_take_the_precise_path(n_bits, snr):
-    """Observations that are not quantiser outputs (here: raw y declared as 1-bit / 2-bit) are not
-    exact in fp16; the kernel detects that per wave and splits y too — results stay within tolerance."""
+    """Observations that are not quantiser outputs (here: raw y declared as 1-bit / 2-bit) through the default FP64
+    kernels, which take any y as it is.  The fast family's exact / inexact y paths (k_y_exact, the y_hi + y_lo
+    split): tests/test_gpu_fast.py."""
     _gpu_or_skip()
     from oracle import qce_oracle as O
     from quantized_channel_estimation_amd import Gmm_nbit, inputs
@@ -262,7 +264,8 @@ def test_ragged_and_tiny_batches():
         assert rel_fro(hg, ho) < H_TOL, (B, rel_fro(hg, ho))
 
 
-# ---- large padded shapes (chunk-streamed kernel, qce_estimate_h2x.hip; FP64 lp + weighted selective modes)
+# ---- large padded shapes with the default precision (the FP64 kernel families; FP64 lp + weighted selective modes;
+# the chunk-streamed fp16-split kernel of qce_h2x_kernel.h at these shapes: tests/test_gpu_fast.py)
 @pytest.mark.parametrize("K,N,pilots,B,n_bits,mean", [
     (16, 128, 1, 700, 1, False),        # cfg4 geometry (N = 128), small K / B
     (7, 100, 1, 300, 2, True),          # padded N (100 -> 128), means, 2-bit uniform
@@ -297,7 +300,9 @@ def test_large_shapes_vs_oracle(K, N, pilots, B, n_bits, mean):
 
 @pytest.mark.parametrize("ksplit", ["1", "2", "3", "7"])
 def test_large_shape_k_splits_and_partials(ksplit, monkeypatch):
-    """K splits of the large-shape kernel (merged by k_merge_splits) and its K-shard partial output."""
+    """The K-shard partial output at a large shape with the default precision.  QCE_KSPLIT is read by the fast
+    family's large-shape kernel only (its K splits and k_merge_splits: tests/test_gpu_fast.py); the FP64 kernels
+    must not depend on it."""
     _gpu_or_skip()
     from oracle import qce_oracle as O
     from quantized_channel_estimation_amd import Gmm_nbit, _lib
