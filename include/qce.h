@@ -58,9 +58,18 @@ typedef struct qce_model qce_model;
                                ~1e-7 relative; an opt-in throughput mode) */
 #define QCE_PRECISION_F64 0
 #define QCE_PRECISION_FAST 1
+#define QCE_PRECISION_INT8 2 /* quantised observations (1 bit, uniform 2..7 bits), dense model, padded M, N <= 64: the
+                                tables cut into QCE_OPT_INT8_SLICES base-128 digit planes, exact int32 products on the
+                                i8 MFMA, FP64 recombination / softmax / combine.  Any other model is prepared as under
+                                QCE_PRECISION_F64.  A sample whose scaled observation is not an integer up to 127 gets
+                                NaN in its whole output row; the K-shard partial calls return QCE_ENOTIMPL. */
 #define QCE_OPT_RESERVE_CUS 3 /* CUs the persistent estimate kernels leave free (value >= 0; default 0): room for the
                                  collective kernels of a concurrent communication stream (qce_kshard_create sets it on
                                  the shard's models for RCCL at world > 1).  Keeps the prepared state. */
+
+#define QCE_OPT_INT8_SLICES 4 /* digit planes per table under QCE_PRECISION_INT8: an integer in 3..8 (default 7, the
+                                 smallest count whose error sits on the FP64 rounding floor; each plane less costs a
+                                 factor 128 in accuracy).  Drops the prepared state. */
 
 #define QCE_IO_HOST 0
 #define QCE_IO_DEVICE 1
@@ -157,7 +166,15 @@ int qce_model_structure(qce_model* model, int* n1, int* n2, int* fourier_active)
 #define QCE_KERNEL_BIG 4      /* GEMM path, N or M in (256, 4096] */
 #define QCE_KERNEL_FOURIER 5  /* (block-)circulant models in the Fourier basis */
 #define QCE_KERNEL_FAST 6     /* precision 'fast': fp16 two-term split */
+#define QCE_KERNEL_INT8 7     /* precision 'int8': k_est_all_i8, int8 digit planes on the i8 MFMA */
 int qce_model_kernel(qce_model* model, int* kind);
+
+/* Diagnostics of a model prepared onto QCE_KERNEL_INT8 (QCE_ESTATE otherwise): for component k and y (B,M) c128, the
+ * FP64 sums raw = sum_s 128^s (D_s ti) of the two digit-plane products before the power-of-two row scale and before
+ * 1 / y_scale -- raw_L (B, 2 MP) and raw_W (B, 2 NP), MP / NP the padded M / N (16, 32 or 64) -- and the row exponents
+ * exps (2 MP + 2 NP ints: E(Linv_k) rows, then E(W_k) rows).  Host pointers, any output may be NULL; synchronises. */
+int qce_debug_i8_products(qce_model* model, const double* y, int64_t B, int k, double* raw_L, double* raw_W,
+                          int* exps);
 
 /* Observations on the device (model-free): `get_observation_nbit` (utils.py:241-251) with `quant`
  * (utils.py:189-203):  y = Q(A h + noise_scale * w).

@@ -19,7 +19,8 @@ MODE_ALL, MODE_TOPN, MODE_CUMP = 0, 1, 2
 OPT_BETA_FIRST = 1
 OPT_PRECISION = 2
 OPT_RESERVE_CUS = 3
-PRECISION_F64, PRECISION_FAST = 0, 1
+PRECISION_F64, PRECISION_FAST, PRECISION_INT8 = 0, 1, 2
+OPT_INT8_SLICES = 4
 QUANT_UNIFORM, QUANT_LLOYD, QUANT_OTHER = 0, 1, 2
 IO_HOST, IO_DEVICE = 0, 1
 OUT_Y, OUT_FEATURES_RAW, OUT_FEATURES_DFT = 0, 1, 2
@@ -87,6 +88,7 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "qce_synchronize": (ctypes.c_int, [_vp]),
     "qce_model_kernel": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "qce_debug_i8_products": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
     "qce_host_alloc": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "qce_host_free": (ctypes.c_int, [_vp]),
     "qce_observe": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
@@ -496,12 +498,32 @@ class DeviceModel:
         check(load().qce_get_tables(self._h, None, None, None, None, None, None, None, ptr(c)))
         return c
 
-    def set_precision(self, precision):
-        """'f64' (default: the reference's complex128 arithmetic) or 'fast' (fp16 two-term split products,
-        fp32 accumulation) for the dense 'all' mode and the K-shard partial."""
-        val = {"f64": PRECISION_F64, "fast": PRECISION_FAST}[precision]
+    def set_precision(self, precision, slices=None):
+        """'f64' (default: the reference's complex128 arithmetic), 'fast' (fp16 two-term split products,
+        fp32 accumulation) or 'int8' (quantised observations: `slices` = 3..8 base-128 digit planes per table, default
+        7, exact int32 products on the i8 MFMA, everything else FP64) for the dense 'all' mode and the K-shard
+        partial.  An 'int8' model the int8 kernel does not cover (n_bits = inf or >= 8, another quantiser, padded M
+        or N beyond 64, the Fourier path) is prepared as under 'f64'; `kernel()` tells."""
+        val = {"f64": PRECISION_F64, "fast": PRECISION_FAST, "int8": PRECISION_INT8}[precision]
+        if slices is not None and precision != "int8":
+            raise ValueError("slices belongs to precision 'int8'")
+        if precision == "int8":
+            self.set_option(OPT_INT8_SLICES, 7 if slices is None else slices)
         self.set_option(OPT_PRECISION, val)
         self.precision = precision
+
+    def debug_i8_products(self, y, k):
+        """Raw digit-plane sums of component k on the int8 kernel (qce_debug_i8_products): (raw_L (B, 2 MP), raw_W
+        (B, 2 NP), exps (2 MP + 2 NP,) int32), before the power-of-two row scale and 1 / y_scale."""
+        y = np.ascontiguousarray(y, dtype=np.complex128)
+        if y.ndim != 2 or y.shape[1] != self.M:
+            raise ValueError(f"y must be (B, {self.M}), got {y.shape}")
+        B = y.shape[0]
+        pad = lambda v: next(p for p in (16, 32, 64, 128, 256) if v <= p)
+        RL, RW = 2 * pad(self.M), 2 * pad(self.N)
+        raw_l, raw_w, exps = np.empty((B, RL)), np.empty((B, RW)), np.empty(RL + RW, dtype=np.int32)
+        check(load().qce_debug_i8_products(self._h, ptr(y), int(B), int(k), ptr(raw_l), ptr(raw_w), ptr(exps)))
+        return raw_l, raw_w, exps
 
     def reserve_cus(self, n):
         """CUs the persistent estimate kernels leave free for a concurrent communication stream (QCE_OPT_RESERVE_CUS;
@@ -544,7 +566,7 @@ class DeviceModel:
     def synchronize(self):
         check(load().qce_synchronize(self._h))
 
-    KERNELS = {0: "none", 1: "f64_4m", 2: "f64_3m", 3: "f64_wide", 4: "big", 5: "fourier", 6: "fast"}
+    KERNELS = {0: "none", 1: "f64_4m", 2: "f64_3m", 3: "f64_wide", 4: "big", 5: "fourier", 6: "fast", 7: "int8"}
 
     def kernel(self):
         """'all'-mode kernel family of the last prepare (qce_model_kernel): f64_3m, f64_4m, fourier, ..."""

@@ -70,6 +70,11 @@ double uniform_step(double snr_db, int nb);
 // Arithmetic of the dense 'all' / partial path for this model: the model option, overridden by
 // QCE_KERNEL=f64 | h2 | f32 (A/B runs).
 bool want_f64(const qce_model* m);
+// The model asks for the int8 family (QCE_PRECISION_INT8 and no QCE_KERNEL override); select_backend grants it where
+// the quantiser and the shape allow, and falls back to the f64 families elsewhere.
+bool want_int8(const qce_model* m);
+// FP64 raw sums of one component on the int8 kernel (qce_debug_i8_products)
+int run_i8_debug(qce_model* m, const double2* dy, long long B, int k, double* rawL, double* rawW, hipStream_t st);
 QceFftEstArgs fft_args(qce_model* m, const double2* y, long long B);
 // stage host input (io == HOST) or use the device pointer directly
 int stage_input(qce_model* m, const double* y, long long B, int io, hipStream_t st, const double2** dy);

@@ -211,6 +211,7 @@ int qce_model_kernel(qce_model* m, int* kind) {
     case QCE_BE_F64_3M_128: *kind = QCE_KERNEL_F64_3M; break;
     case QCE_BE_F64_WIDE: *kind = QCE_KERNEL_F64_WIDE; break;
     case QCE_BE_FAST: *kind = QCE_KERNEL_FAST; break;
+    case QCE_BE_INT8: *kind = QCE_KERNEL_INT8; break;
   }
   return QCE_OK;
 }
@@ -229,8 +230,16 @@ int qce_model_set_option(qce_model* m, int option, double value) {
     return QCE_OK;
   }
   if (option == QCE_OPT_PRECISION) {
-    if (value != QCE_PRECISION_F64 && value != QCE_PRECISION_FAST) return qce_set_error(QCE_EARG, "unknown precision");
+    if (value != QCE_PRECISION_F64 && value != QCE_PRECISION_FAST && value != QCE_PRECISION_INT8)
+      return qce_set_error(QCE_EARG, "unknown precision");
     m->precision = (int)value;
+    m->prepared = 0;
+    return QCE_OK;
+  }
+  if (option == QCE_OPT_INT8_SLICES) {
+    if (!(value >= 3.0 && value <= 8.0) || value != floor(value))
+      return qce_set_error(QCE_EARG, "int8 slices must be an integer in 3..8");
+    m->int8_slices = (int)value;
     m->prepared = 0;
     return QCE_OK;
   }

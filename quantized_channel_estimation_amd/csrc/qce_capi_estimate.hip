@@ -14,7 +14,15 @@ bool want_f64(const qce_model* m) {
   const char* e = getenv("QCE_KERNEL");
   if (e && strcmp(e, "f64") == 0) return true;
   if (e && (strcmp(e, "h2") == 0 || strcmp(e, "f32") == 0)) return false;
+  // an int8 model that fell back (quantiser, shape, structure) is an f64 model in every respect
+  if (m->precision == QCE_PRECISION_INT8) return m->backend != QCE_BE_INT8;
   return m->precision == QCE_PRECISION_F64;
+}
+
+bool want_int8(const qce_model* m) {
+  const char* e = getenv("QCE_KERNEL");
+  if (e && (strcmp(e, "f64") == 0 || strcmp(e, "h2") == 0 || strcmp(e, "f32") == 0)) return false;
+  return m->precision == QCE_PRECISION_INT8;
 }
 
 namespace {
@@ -265,7 +273,39 @@ int run_h2x(qce_model* m, const double2* dy, long long B, double2* h, double* om
   return QCE_OK;
 }
 
+QceI8Args i8_args(qce_model* m, const double2* dy, long long B) {
+  QceI8Args a;
+  set_shape(a, m, B);
+  a.S = m->i8_S;
+  a.group = m->i8_group;
+  a.y_scale = m->y_scale;
+  a.y = dy;
+  a.planes = m->i8_planes.p;
+  a.pstride = qce_pack_i8_bytes(m->MP, m->NP, m->i8_S);
+  a.rowtab = m->i8_rowtab.p;
+  a.cconst = m->cconst.p;
+  a.h = nullptr;
+  return a;
+}
+
+// 'all' mode on the int8 digit planes (qce_estimate_i8.hip): one workgroup per sample tile, final h only
+int run_i8(qce_model* m, const double2* dy, long long B, double2* h, hipStream_t st) {
+  QceI8Args a = i8_args(m, dy, B);
+  a.h = h;
+  HIPCHK(qce_launch_est_i8(a, st));
+  return QCE_OK;
+}
+
 }  // namespace
+
+int run_i8_debug(qce_model* m, const double2* dy, long long B, int k, double* rawL, double* rawW, hipStream_t st) {
+  QceI8Args a = i8_args(m, dy, B);
+  a.dbg_k = k;
+  a.dbgL = rawL;
+  a.dbgW = rawW;
+  HIPCHK(qce_launch_est_i8(a, st));
+  return QCE_OK;
+}
 
 // stage host input (io == HOST) or use the device pointer directly
 int stage_input(qce_model* m, const double* y, long long B, int io, hipStream_t st, const double2** dy) {
@@ -349,6 +389,8 @@ int run_all(qce_model* m, const double2* dy, long long B, const AllOut& o, hipSt
   const bool f64_family = be == QCE_BE_BIG || be == QCE_BE_F64_4M || be == QCE_BE_F64_3M ||
                           be == QCE_BE_F64_3M_128 || be == QCE_BE_F64_WIDE;
   const long long nacc = B * 2 * m->N;
+  if (be == QCE_BE_INT8 && o.kind != AllOut::FINAL)
+    return qce_set_error(QCE_ENOTIMPL, "K-shard partials are not covered by the int8 precision");
   if (o.kind == AllOut::SHIFTED && !f64_family) {  // their (m, s, acc) partial, scaled and packed
     HIPCHK(m->m_scr.ensure((size_t)B));
     HIPCHK(m->s_scr.ensure((size_t)B));
@@ -411,6 +453,8 @@ int run_all(qce_model* m, const double2* dy, long long B, const AllOut& o, hipSt
       return run_f64(m, dy, B, o.h, o.om, o.os, static_cast<double*>(o.oa), st, o.pk, o.shift);
     case QCE_BE_F64_WIDE:
       return run_wide(m, dy, B, wmode, o.h, o.om, o.os, static_cast<double*>(o.oa), o.pk, o.shift, st);
+    case QCE_BE_INT8:
+      return run_i8(m, dy, B, o.h, st);
     case QCE_BE_FAST: {
       if (fast_uses_h2(m)) return run_h2(m, dy, B, o.h, o.om, o.os, static_cast<float*>(o.oa), st);
       if (int rc = ensure_packs(m, st)) return rc;

@@ -45,7 +45,8 @@ bool is_identity(const double* A, int M, int N) {
 
 // The one place a prepare's kernel family is chosen.  fourier_ok: the observation matrix is the identity and the
 // call is not the dense replay of ensure_dense.  A dense family also gets its padded shape (MP, NP).
-QceBackend select_backend(const qce_model* m, int M, bool fourier_ok, int* MP, int* NP) {
+// int8_ok: the quantiser's outputs are integers up to 127 after one scale (1 bit, or uniform with 2..7 bits).
+QceBackend select_backend(const qce_model* m, int M, bool fourier_ok, bool int8_ok, int* MP, int* NP) {
   *MP = *NP = 0;
   if (fourier_ok && m->fft_n1 > 0 && fft_enabled() && !m->beta_first) return QCE_BE_FOURIER;
   if (pad_dim(M) < 0 || pad_dim(m->N) < 0) return QCE_BE_BIG;
@@ -55,7 +56,9 @@ QceBackend select_backend(const qce_model* m, int M, bool fourier_ok, int* MP, i
     *MP = *MP < 64 ? 64 : *MP;
     *NP = *NP < 64 ? 64 : *NP;
   }
-  if (want_f64(m)) {
+  // the int8 family where it applies; everywhere else an int8 model takes the family it would take under f64
+  if (want_int8(m) && int8_ok && qce_i8_shape(*MP, *NP)) return QCE_BE_INT8;
+  if (want_f64(m) || want_int8(m)) {
     if (qce_f64_shape(*MP, *NP))  // the 3M layout where a 3M kernel covers the shape
       return qce_f64g_shape(*MP, *NP) ? QCE_BE_F64_3M : (qce_f64h_shape(*MP, *NP) ? QCE_BE_F64_3M_128 : QCE_BE_F64_4M);
     if (qce_wsum_shape(*MP, *NP)) return QCE_BE_F64_WIDE;
@@ -183,7 +186,8 @@ static int prepare_impl(qce_model* m, const double* A, int M, double snr_db, dou
   // an explicit identity is the same observation model (and takes the same fast path: bitwise the same Cy)
   const bool idA = !A || is_identity(A, M, N);
   int MP, NP;
-  const QceBackend be = select_backend(m, M, idA && !tables_only, &MP, &NP);
+  const bool int8_ok = kind == 0 || (kind == 1 && quant_kind == QCE_QUANT_UNIFORM && nb >= 2 && nb <= 7);
+  const QceBackend be = select_backend(m, M, idA && !tables_only, int8_ok, &MP, &NP);
   m->last.M = M;
   m->last.snr_db = snr_db;
   m->last.n_bits = n_bits;
@@ -377,6 +381,20 @@ static int prepare_impl(qce_model* m, const double* A, int M, double snr_db, dou
       HIPCHK(qce_launch_pack_f64all(K, M, N, MP, NP, m->has_mean, m->Linv.p, m->W.p, m->q0.p, m->bvec.p,
                                     reinterpret_cast<double*>(m->pack_f64.p), st));
       break;
+    case QCE_BE_INT8: {
+      // digit planes of E(Linv_k), E(W_k); the observation scale that makes the quantiser outputs integers
+      const double y_scale = kind == 0 ? sqrt(2.0) : 2.0 / delta;
+      const int S = m->int8_slices;
+      HIPCHK(m->i8_planes.ensure((size_t)qce_pack_i8_bytes(MP, NP, S) * K));
+      HIPCHK(m->i8_rowtab.ensure((size_t)(4 * MP + 4 * NP) * K));
+      HIPCHK(m->i8_exps.ensure((size_t)(2 * MP + 2 * NP) * K));
+      HIPCHK(qce_launch_pack_i8(K, M, N, MP, NP, S, y_scale, m->Linv.p, m->W.p, m->q0.p, m->bvec.p, m->i8_planes.p,
+                                m->i8_rowtab.p, m->i8_exps.p, st));
+      m->i8_S = S;
+      m->i8_group = kind == 0 ? 3 : 2;
+      m->y_scale = y_scale;
+      break;
+    }
     case QCE_BE_FAST: {
       // FP16 two-term split tables; the observation scale makes quantiser outputs exact in fp16
       // (1 bit: y sqrt(2) = +-1; uniform: y 2/delta = odd integers), folded into the slice scales

@@ -87,6 +87,33 @@ hipError_t qce_launch_pack_h2(int K, int M, int N, int MP, int NP, int has_mean,
 hipError_t qce_launch_est_h2(const QceH2Args& a, bool out_partial, hipStream_t st);
 int qce_h2_blocks_per_cu(int MP, int NP, int has_mean);
 
+// Int8-slice 'all' kernel for quantised observations (qce_estimate_i8.hip): padded M, N <= 64, one workgroup per
+// tile of qce_i8_tile(MP, NP) samples over all K components
+struct QceI8Args {
+  long long B;
+  int M, N, K, MP, NP, has_mean;
+  int S;      // digit planes per table (3..8)
+  int group;  // planes combined in int32 before the FP64 recombination (2; 3 at 1 bit)
+  double y_scale;
+  const double2* y;
+  const signed char* planes;  // K x pstride bytes, fragment-major (see the kernel file)
+  long long pstride;
+  const double* rowtab;  // K x [scale_L (2MP) | q0 (2MP) | scale_W (2NP) | b (2NP)]
+  const double* cconst;
+  double2* h;
+  // debug launch (dbgL != nullptr): the FP64 raw sums of component dbg_k, (B, 2MP) and (B, 2NP), instead of h
+  int dbg_k = 0;
+  double *dbgL = nullptr, *dbgW = nullptr;
+};
+bool qce_i8_shape(int MP, int NP);
+int qce_i8_tile(int MP, int NP);  // samples per workgroup
+long long qce_pack_i8_bytes(int MP, int NP, int S);  // per component
+// k_pack_i8: digit planes, row tables and row exponents (K x (2MP + 2NP) ints) from the resident FP64 tables
+hipError_t qce_launch_pack_i8(int K, int M, int N, int MP, int NP, int S, double y_scale, const double2* Linv,
+                              const double2* W, const double2* q0, const double2* bvec, signed char* planes,
+                              double* rowtab, int* exps, hipStream_t st);
+hipError_t qce_launch_est_i8(const QceI8Args& a, hipStream_t st);
+
 // FP64 fused 'all' kernel (qce_estimate_f64.hip): the reference-precision path, stream-K scheduled
 struct QceF64Args {
   long long B;

@@ -46,6 +46,7 @@ enum QceBackend {
   QCE_BE_F64_3M_128,   // 3M layout at padded 128 (k_est_all_f64h)
   QCE_BE_F64_WIDE,     // beyond padded 128: the two-pass FP64 path (qce_wsum_f64.hip)
   QCE_BE_FAST,         // fp16-split / FP32-MFMA kernels (QCE_KERNEL picks between them per launch)
+  QCE_BE_INT8,         // int8 digit planes on the i8 MFMA, quantised observations, padded <= 64 (k_est_all_i8)
 };
 
 struct qce_model {
@@ -59,6 +60,7 @@ struct qce_model {
   QcePrepareArgs pack_args{};
   int beta_first = 0;  // QCE_OPT_BETA_FIRST: multi-bit Cr mixes with the first gain (blmmse.py:53, :86)
   int precision = QCE_PRECISION_F64;  // QCE_OPT_PRECISION: arithmetic of the dense 'all' / partial path
+  int int8_slices = 7;  // QCE_OPT_INT8_SLICES: digit planes per table under QCE_PRECISION_INT8
   hipStream_t stream = nullptr;
   int has_mean = 0;
   std::vector<double> weights;
@@ -91,6 +93,11 @@ struct qce_model {
   DevBuf<double> sp_m, sp_s;
   DevBuf<float> sp_a;
   DevBuf<int> yflag;
+  // int8 digit planes, row tables and row exponents (qce_estimate_i8.hip); i8_group: planes combined in int32
+  DevBuf<signed char> i8_planes;
+  DevBuf<double> i8_rowtab;
+  DevBuf<int> i8_exps;
+  int i8_S = 0, i8_group = 2;
   // FP64 fused-kernel tables (qce_estimate_f64.hip) and its cut-tile scratch
   DevBuf<char> pack_f64;
   DevBuf<char> pack_ws;  // ... and of the two-pass path (qce_wsum_f64.hip)

@@ -162,8 +162,10 @@ class Gmm_nbit:
         self.F2 = None
         self.device = device
         # arithmetic of the dense 'all' mode: "f64" = the reference's complex128 (FP64 MFMA products and
-        # accumulation, the default), "fast" = fp16 two-term split products with fp32 accumulation (opt-in)
+        # accumulation, the default), "fast" = fp16 two-term split products with fp32 accumulation (opt-in), "int8" =
+        # int8_slices digit planes of the tables on the i8 MFMA for quantised observations (opt-in; FP64 elsewhere)
         self.precision = precision
+        self.int8_slices = 7
         self.mirror_state = True
         self._dev = None
         self._dev_key = None
@@ -309,11 +311,12 @@ class Gmm_nbit:
         means = self.means_cplx
         w = np.asarray(self.gm.weights_, dtype=float)
         precision = getattr(self, "precision", "f64")
-        key = (self._param_digest(covs, means, w), self.device, precision)
+        slices = int(getattr(self, "int8_slices", 7)) if precision == "int8" else None
+        key = (self._param_digest(covs, means, w), self.device, precision, slices)
         if self._dev is None or self._dev_key != key:
             self._dev = _lib.DeviceModel(means, covs, w, device=self.device)
             if precision != "f64":
-                self._dev.set_precision(precision)
+                self._dev.set_precision(precision, **({} if slices is None else {"slices": slices}))
             self._dev_key = key
             self._state = None
         return self._dev
