@@ -71,6 +71,14 @@ typedef struct qce_model qce_model;
                                  smallest count whose error sits on the FP64 rounding floor; each plane less costs a
                                  factor 128 in accuracy).  Drops the prepared state. */
 
+#define QCE_OPT_FOURIER_PILOTS 5 /* value != 0 (default 0): a (block-)circulant model observed through A = kron(x, I_N)
+                                    with 2 <= P <= 4 pilots, N a power of two in 16..256 and P N <= 512 is prepared
+                                    and estimated in the Fourier domain (per-bin P x P tables, QCE_KERNEL_FOURIER_PILOTS)
+                                    instead of the dense families at M = P N.  A must be exactly kron(x, I_N): every
+                                    off-diagonal entry of every N x N block zero (no tolerance), one value on each
+                                    block's diagonal.  Anything else is prepared as without the option.  The K-shard partial
+                                    calls return QCE_ENOTIMPL on such a prepare.  Drops the prepared state. */
+
 #define QCE_IO_HOST 0
 #define QCE_IO_DEVICE 1
 
@@ -156,6 +164,8 @@ int qce_model_info(qce_model* model, int* K, int* N, int* M, int* device);
 /* Structure of the mixture found at creation: every C_k is block-circulant for kron(F_n1, F_n2) (n1 = 1:
  * circulant, the fits of gmm_cplx_bussgang.py:104-133), or n1 = n2 = 0.  With A = I such a model is
  * prepared and estimated in the Fourier domain (per-bin tables; fourier_active = 1 after such a prepare).
+ * With QCE_OPT_FOURIER_PILOTS set the same holds for A = kron(x, I_N), 2 <= P <= 4 pilots (per-bin P x P tables;
+ * fourier_active = 1, qce_model_kernel reports QCE_KERNEL_FOURIER_PILOTS).
  * Environment QCE_FFT=0 keeps every prepare on the dense path. */
 int qce_model_structure(qce_model* model, int* n1, int* n2, int* fourier_active);
 /* The 'all'-mode kernel family the last prepare selected (diagnostics, benchmarks): */
@@ -167,6 +177,7 @@ int qce_model_structure(qce_model* model, int* n1, int* n2, int* fourier_active)
 #define QCE_KERNEL_FOURIER 5  /* (block-)circulant models in the Fourier basis */
 #define QCE_KERNEL_FAST 6     /* precision 'fast': fp16 two-term split */
 #define QCE_KERNEL_INT8 7     /* precision 'int8': k_est_all_i8, int8 digit planes on the i8 MFMA */
+#define QCE_KERNEL_FOURIER_PILOTS 8 /* (block-)circulant models with A = kron(x, I_N) in the Fourier basis */
 int qce_model_kernel(qce_model* model, int* kind);
 
 /* Diagnostics of a model prepared onto QCE_KERNEL_INT8 (QCE_ESTATE otherwise): for component k and y (B,M) c128, the

@@ -21,6 +21,7 @@ OPT_PRECISION = 2
 OPT_RESERVE_CUS = 3
 PRECISION_F64, PRECISION_FAST, PRECISION_INT8 = 0, 1, 2
 OPT_INT8_SLICES = 4
+OPT_FOURIER_PILOTS = 5
 QUANT_UNIFORM, QUANT_LLOYD, QUANT_OTHER = 0, 1, 2
 IO_HOST, IO_DEVICE = 0, 1
 OUT_Y, OUT_FEATURES_RAW, OUT_FEATURES_DFT = 0, 1, 2
@@ -330,6 +331,7 @@ class DeviceModel:
         self.K, self.N, self.device = K, N, int(device)
         self.M = 0
         self.precision = "f64"
+        self.fourier_pilots = False
         self.has_mean = bool(means is not None and np.any(means != 0))
 
     @property
@@ -512,6 +514,13 @@ class DeviceModel:
         self.set_option(OPT_PRECISION, val)
         self.precision = precision
 
+    def set_fourier_pilots(self, on=True):
+        """Opt in to the Fourier-domain path for A = kron(x, I_N) (QCE_OPT_FOURIER_PILOTS): a (block-)circulant model
+        with 2..4 pilots is then prepared per DFT bin instead of densely at M = P N; `kernel()` tells.  The K-shard
+        partial calls raise NotImplementedError on such a prepare."""
+        self.set_option(OPT_FOURIER_PILOTS, 1.0 if on else 0.0)
+        self.fourier_pilots = bool(on)
+
     def debug_i8_products(self, y, k):
         """Raw digit-plane sums of component k on the int8 kernel (qce_debug_i8_products): (raw_L (B, 2 MP), raw_W
         (B, 2 NP), exps (2 MP + 2 NP,) int32), before the power-of-two row scale and 1 / y_scale."""
@@ -566,7 +575,8 @@ class DeviceModel:
     def synchronize(self):
         check(load().qce_synchronize(self._h))
 
-    KERNELS = {0: "none", 1: "f64_4m", 2: "f64_3m", 3: "f64_wide", 4: "big", 5: "fourier", 6: "fast", 7: "int8"}
+    KERNELS = {0: "none", 1: "f64_4m", 2: "f64_3m", 3: "f64_wide", 4: "big", 5: "fourier", 6: "fast", 7: "int8",
+               8: "fourier_pilots"}
 
     def kernel(self):
         """'all'-mode kernel family of the last prepare (qce_model_kernel): f64_3m, f64_4m, fourier, ..."""
@@ -576,7 +586,7 @@ class DeviceModel:
 
     def structure(self):
         """(n1, n2, fourier_active): block-circulant structure found at creation ((0, 0) if none) and
-        whether the last prepare took the Fourier-domain path (qce_fft.hip)."""
+        whether the last prepare took a Fourier-domain path (qce_fft.hip; qce_fft_pilot.hip with pilots)."""
         a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(load().qce_model_structure(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value

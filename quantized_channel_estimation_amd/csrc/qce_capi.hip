@@ -194,7 +194,7 @@ int qce_model_structure(qce_model* m, int* n1, int* n2, int* fourier_active) {
   if (!m) return qce_set_error(QCE_EARG, "null model");
   if (n1) *n1 = m->fft_n1;
   if (n2) *n2 = m->fft_n2;
-  if (fourier_active) *fourier_active = m->prepared && m->backend == QCE_BE_FOURIER;
+  if (fourier_active) *fourier_active = m->prepared && qce_be_fourier(m->backend);
   return QCE_OK;
 }
 
@@ -212,6 +212,7 @@ int qce_model_kernel(qce_model* m, int* kind) {
     case QCE_BE_F64_WIDE: *kind = QCE_KERNEL_F64_WIDE; break;
     case QCE_BE_FAST: *kind = QCE_KERNEL_FAST; break;
     case QCE_BE_INT8: *kind = QCE_KERNEL_INT8; break;
+    case QCE_BE_FOURIER_PILOTS: *kind = QCE_KERNEL_FOURIER_PILOTS; break;
   }
   return QCE_OK;
 }
@@ -233,6 +234,11 @@ int qce_model_set_option(qce_model* m, int option, double value) {
     if (value != QCE_PRECISION_F64 && value != QCE_PRECISION_FAST && value != QCE_PRECISION_INT8)
       return qce_set_error(QCE_EARG, "unknown precision");
     m->precision = (int)value;
+    m->prepared = 0;
+    return QCE_OK;
+  }
+  if (option == QCE_OPT_FOURIER_PILOTS) {
+    m->fourier_pilots = value != 0.0;
     m->prepared = 0;
     return QCE_OK;
   }

@@ -319,6 +319,26 @@ int stage_input(qce_model* m, const double* y, long long B, int io, hipStream_t 
   return QCE_OK;
 }
 
+QceFftpEstArgs fftp_args(qce_model* m, const double2* y, long long B) {
+  QceFftpEstArgs a;
+  a.B = B;
+  a.N = m->N;
+  a.n1 = m->fft_n1;
+  a.n2 = m->fft_n2;
+  a.K = m->K;
+  a.Kp = qce_fftp_kpad(m->K);
+  a.P = m->fp_P;
+  a.has_mean = m->has_mean;
+  a.y = y;
+  a.tabL = m->fp_tabL.p;
+  a.cprime = m->fp_cprime.p;
+  a.tabW = m->fp_tabW.p;
+  a.wts = nullptr;
+  a.h = nullptr;
+  a.lp = nullptr;
+  return a;
+}
+
 QceFftEstArgs fft_args(qce_model* m, const double2* y, long long B) {
   QceFftEstArgs a;
   a.B = B;
@@ -391,6 +411,9 @@ int run_all(qce_model* m, const double2* dy, long long B, const AllOut& o, hipSt
   const long long nacc = B * 2 * m->N;
   if (be == QCE_BE_INT8 && o.kind != AllOut::FINAL)
     return qce_set_error(QCE_ENOTIMPL, "K-shard partials are not covered by the int8 precision");
+  if (be == QCE_BE_FOURIER_PILOTS && o.kind != AllOut::FINAL)
+    return qce_set_error(QCE_ENOTIMPL, "K-shard partials are not covered by the Fourier path with pilots "
+                                       "(QCE_OPT_FOURIER_PILOTS)");
   if (o.kind == AllOut::SHIFTED && !f64_family) {  // their (m, s, acc) partial, scaled and packed
     HIPCHK(m->m_scr.ensure((size_t)B));
     HIPCHK(m->s_scr.ensure((size_t)B));
@@ -455,6 +478,12 @@ int run_all(qce_model* m, const double2* dy, long long B, const AllOut& o, hipSt
       return run_wide(m, dy, B, wmode, o.h, o.om, o.os, static_cast<double*>(o.oa), o.pk, o.shift, st);
     case QCE_BE_INT8:
       return run_i8(m, dy, B, o.h, st);
+    case QCE_BE_FOURIER_PILOTS: {  // qce_fft_pilot.hip: final h only
+      QceFftpEstArgs fa = fftp_args(m, dy, B);
+      fa.h = o.h;
+      HIPCHK(qce_launch_fftp_est(fa, 0, st));
+      return QCE_OK;
+    }
     case QCE_BE_FAST: {
       if (fast_uses_h2(m)) return run_h2(m, dy, B, o.h, o.om, o.os, static_cast<float*>(o.oa), st);
       if (int rc = ensure_packs(m, st)) return rc;
@@ -475,6 +504,13 @@ int weighted_sum(qce_model* m, const double2* y, long long B, const double* w, d
     fa.wts = w;
     fa.h = h;
     HIPCHK(qce_launch_fft_est(fa, 2, st));
+    return QCE_OK;
+  }
+  if (m->backend == QCE_BE_FOURIER_PILOTS) {
+    QceFftpEstArgs fa = fftp_args(m, y, B);
+    fa.wts = w;
+    fa.h = h;
+    HIPCHK(qce_launch_fftp_est(fa, 2, st));
     return QCE_OK;
   }
   if (m->backend == QCE_BE_BIG) return qce_big_wsum(m, y, B, w, h, m->N, st);
@@ -527,6 +563,12 @@ int backend_lp(qce_model* m, const double2* x, long long B, double* lp, hipStrea
     HIPCHK(qce_launch_fft_est(fa, 1, st));
     return QCE_OK;
   }
+  if (m->backend == QCE_BE_FOURIER_PILOTS) {
+    QceFftpEstArgs fa = fftp_args(m, x, B);
+    fa.lp = lp;
+    HIPCHK(qce_launch_fftp_est(fa, 1, st));
+    return QCE_OK;
+  }
   if (m->backend == QCE_BE_BIG) return qce_big_lp(m, x, B, lp, st);
   if (int rc = ensure_packs(m, st)) return rc;
   QceEstArgs a = est_args(m, x, B);
@@ -543,7 +585,7 @@ int qce_estimate(qce_model* m, const double* y, int64_t B, int mode, double mode
   if (B < 0 || (B > 0 && (!y || !h_out))) return qce_set_error(QCE_EARG, "bad y / h_out");
   if (B == 0) return QCE_OK;
   const QceBackend be = m->backend;
-  const bool dense = be != QCE_BE_FOURIER && be != QCE_BE_BIG;  // the fused-kernel families over padded tables
+  const bool dense = !qce_be_fourier(be) && be != QCE_BE_BIG;  // the fused-kernel families over padded tables
   if (dense && mode != QCE_MODE_ALL && !qce_select_shape_supported(m->MP, m->NP))
     return qce_set_error(QCE_ENOTIMPL, "selective modes: shape not covered");
   if (mode != QCE_MODE_ALL && m->K > qce_select_max_k())

@@ -405,7 +405,8 @@ static int assigned_impl(qce_model* m, const double* y, int64_t B, const int64_t
   if (B < 0 || (B > 0 && (!y || !h_out))) return qce_set_error(QCE_EARG, "bad arguments");
   if (!comp && B > m->K) return qce_set_error(QCE_EARG, "without comp, sample b uses component b: B <= K");
   if (B == 0) return QCE_OK;
-  if (m->backend == QCE_BE_BIG) return qce_set_error(QCE_ENOTIMPL, "per-sample filters / LS cover N, M <= 256");
+  if (m->backend == QCE_BE_BIG || m->M > 256)
+    return qce_set_error(QCE_ENOTIMPL, "per-sample filters / LS cover N, M <= 256");
   if ((rc = ensure_dense(m))) return rc;
   DeviceGuard g(m->device);
   hipStream_t st = pick_stream(m, stream);

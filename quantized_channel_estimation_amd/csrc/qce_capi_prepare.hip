@@ -43,12 +43,37 @@ bool is_identity(const double* A, int M, int N) {
   return true;
 }
 
+// A (M x N, interleaved complex) is exactly kron(x, I_N): M = P N, every off-diagonal entry of every N x N block is
+// zero (+0 or -0: np.kron(x, I) yields -0 where x has a negative part, and either gives the same Cy) and the
+// diagonal of block p is one value x_p.  Returns P and fills x for P <= 4 (the widest the Fourier family takes),
+// 0 otherwise.
+int pilot_vector(const double* A, int M, int N, double2* x) {
+  if (!A || M % N != 0) return 0;
+  const int P = M / N;
+  if (P > 4) return 0;
+  for (int p = 0; p < P; ++p) {
+    const double* blk = A + 2 * (size_t)p * N * N;
+    const double xr = blk[0], xi = blk[1];
+    for (int i = 0; i < N; ++i)
+      for (int j = 0; j < N; ++j) {
+        const double re = blk[2 * ((size_t)i * N + j)], im = blk[2 * ((size_t)i * N + j) + 1];
+        if (i == j ? (re != xr || im != xi) : (re != 0.0 || im != 0.0)) return 0;
+      }
+    x[p] = make_double2(xr, xi);
+  }
+  return P;
+}
+
 // The one place a prepare's kernel family is chosen.  fourier_ok: the observation matrix is the identity and the
-// call is not the dense replay of ensure_dense.  A dense family also gets its padded shape (MP, NP).
+// call is not the dense replay of ensure_dense.  pilots: P when A = kron(x, I_N) with P <= 4 pilots (and the call is
+// not that replay), else 0.  A dense family also gets its padded shape (MP, NP).
 // int8_ok: the quantiser's outputs are integers up to 127 after one scale (1 bit, or uniform with 2..7 bits).
-QceBackend select_backend(const qce_model* m, int M, bool fourier_ok, bool int8_ok, int* MP, int* NP) {
+QceBackend select_backend(const qce_model* m, int M, bool fourier_ok, int pilots, bool int8_ok, int* MP, int* NP) {
   *MP = *NP = 0;
   if (fourier_ok && m->fft_n1 > 0 && fft_enabled() && !m->beta_first) return QCE_BE_FOURIER;
+  if (m->fourier_pilots && pilots >= 2 && m->fft_n1 > 0 && fft_enabled() && !m->beta_first &&
+      qce_fftp_shape(m->N, pilots, m->K))
+    return QCE_BE_FOURIER_PILOTS;
   if (pad_dim(M) < 0 || pad_dim(m->N) < 0) return QCE_BE_BIG;
   *MP = pad_dim(M);
   *NP = pad_dim(m->N);
@@ -187,7 +212,9 @@ static int prepare_impl(qce_model* m, const double* A, int M, double snr_db, dou
   const bool idA = !A || is_identity(A, M, N);
   int MP, NP;
   const bool int8_ok = kind == 0 || (kind == 1 && quant_kind == QCE_QUANT_UNIFORM && nb >= 2 && nb <= 7);
-  const QceBackend be = select_backend(m, M, idA && !tables_only, int8_ok, &MP, &NP);
+  double2 px[4] = {};
+  const int pilots = (!idA && !tables_only && m->fourier_pilots) ? pilot_vector(A, M, N, px) : 0;
+  const QceBackend be = select_backend(m, M, idA && !tables_only, pilots, int8_ok, &MP, &NP);
   m->last.M = M;
   m->last.snr_db = snr_db;
   m->last.n_bits = n_bits;
@@ -258,6 +285,46 @@ static int prepare_impl(qce_model* m, const double* A, int M, double snr_db, dou
     }
     if ((rc = post_status(m, st))) return rc;
     m->M = N;
+    m->backend = be;
+    m->dense_valid = 0;
+    m->prepared = 1;
+    return QCE_OK;
+  }
+  if (be == QCE_BE_FOURIER_PILOTS) {
+    // Fourier-domain prepare with pilots (qce_fft_pilot.hip): per-bin P x P tables only; A is kept for the dense replay
+    const int Kp = qce_fftp_kpad(K);
+    m->last.A.assign(A, A + 2 * (size_t)M * N);
+    HIPCHK(m->fp_tabL.ensure((size_t)qce_fftp_tabl_doubles(N, pilots, Kp, m->has_mean)));
+    HIPCHK(m->fp_tabW.ensure((size_t)qce_fftp_tabw_doubles(N, pilots, Kp, m->has_mean)));
+    HIPCHK(m->fp_cprime.ensure((size_t)Kp));
+    QceFftpPrepArgs fa;
+    fa.N = N;
+    fa.n1 = m->fft_n1;
+    fa.n2 = m->fft_n2;
+    fa.K = K;
+    fa.Kp = Kp;
+    fa.P = pilots;
+    fa.has_mean = m->has_mean;
+    for (int p = 0; p < 4; ++p) fa.x[p] = m->fp_x[p] = px[p];
+    fa.s2 = pow(10.0, -snr_db / 10.0);
+    fa.kind = kind;
+    fa.n_bits = nb;
+    fa.quant_kind = quant_kind;
+    fa.delta = delta;
+    fa.thr = m->thr.p;
+    fa.lab = m->lab.p;
+    fa.logw = m->logw.p;
+    fa.ceig = m->f_ceig.p;
+    fa.col0 = m->f_col0.p;
+    fa.mspec = m->f_mspec.p;
+    fa.tabL = m->fp_tabL.p;
+    fa.cprime = m->fp_cprime.p;
+    fa.tabW = m->fp_tabW.p;
+    fa.status = m->status.p;
+    HIPCHK(qce_launch_fftp_prep(fa, st));
+    if ((rc = post_status(m, st))) return rc;
+    m->fp_P = pilots;
+    m->M = M;
     m->backend = be;
     m->dense_valid = 0;
     m->prepared = 1;
@@ -356,6 +423,7 @@ static int prepare_impl(qce_model* m, const double* A, int M, double snr_db, dou
   switch (be) {
     case QCE_BE_NONE:
     case QCE_BE_FOURIER:  // returned above
+    case QCE_BE_FOURIER_PILOTS:
     case QCE_BE_BIG:
       // GEMM-based FP64 path (qce_big.hip): the dense tables are all it reads; the stacked filters on first use
       break;
@@ -425,8 +493,10 @@ static int prepare_impl(qce_model* m, const double* A, int M, double snr_db, dou
 // The dense tables of a prepare that took the Fourier path, computed when first asked for
 // (qce_get_tables: the reference's gm state mirror); the Fourier tables stay active.
 int ensure_dense(qce_model* m, void* stream) {
-  if (m->backend != QCE_BE_FOURIER || m->dense_valid) return QCE_OK;
-  return prepare_impl(m, nullptr, m->last.M, m->last.snr_db, m->last.n_bits, m->last.quant_kind,
+  if (!qce_be_fourier(m->backend) || m->dense_valid) return QCE_OK;
+  // the pilots family replays with the A it was prepared with (kept on the host)
+  const double* A = m->backend == QCE_BE_FOURIER_PILOTS ? m->last.A.data() : nullptr;
+  return prepare_impl(m, A, m->last.M, m->last.snr_db, m->last.n_bits, m->last.quant_kind,
                       m->last.thr.empty() ? nullptr : m->last.thr.data(),
                       m->last.lab.empty() ? nullptr : m->last.lab.data(), m->last.n_levels, stream, true);
 }

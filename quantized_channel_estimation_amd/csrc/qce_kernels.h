@@ -260,6 +260,37 @@ hipError_t qce_launch_fft_pack(const QceFftEstArgs& a, const double* rinvT, cons
                                const double* wT, const double2* bT, hipStream_t st);
 hipError_t qce_launch_fft_mfma(const QceFftEstArgs& a, int out, hipStream_t st);
 
+// Fourier-domain path with pilots, A = kron(x, I_N), 2 <= P <= 4 (qce_fft_pilot.hip); components padded to Kp
+struct QceFftpPrepArgs {
+  int N, n1, n2, K, Kp, P, has_mean;
+  double2 x[4];  // the pilot vector
+  double s2;
+  int kind, n_bits, quant_kind;
+  double delta;
+  const double *thr, *lab, *logw, *ceig;
+  const double2 *col0, *mspec;
+  double* tabL;    // lp operand [Kp / 16][TL][N][16], TL = P^2 (+ 2 P with means)
+  double* cprime;  // Kp (padding: -inf)
+  double* tabW;    // filter operand [N / 16][TF][Kp][16], TF = 2 P (+ 2 with means)
+  int* status;     // K
+};
+struct QceFftpEstArgs {
+  long long B;
+  int N, n1, n2, K, Kp, P, has_mean;
+  const double2* y;  // B x P N
+  const double *tabL, *cprime, *tabW;
+  const double* wts;  // FP64 selection weights (out = 2)
+  double2* h;
+  double* lp;  // out = 1
+};
+bool qce_fftp_shape(int N, int P, int K);  // the kernels cover (N, P) and the LDS tile fits at K components
+int qce_fftp_kpad(int K);
+long long qce_fftp_tabl_doubles(int N, int P, int Kp, int has_mean);
+long long qce_fftp_tabw_doubles(int N, int P, int Kp, int has_mean);
+hipError_t qce_launch_fftp_prep(const QceFftpPrepArgs& a, hipStream_t st);
+// out: 0 'all' h, 1 lp, 2 weighted h
+hipError_t qce_launch_fftp_est(const QceFftpEstArgs& a, int out, hipStream_t st);
+
 // Observation generation / quantisation (qce_observe.hip; utils.py:189-203, :241-251)
 struct QceObserveArgs {
   long long B;

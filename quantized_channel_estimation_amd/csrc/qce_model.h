@@ -47,7 +47,10 @@ enum QceBackend {
   QCE_BE_F64_WIDE,     // beyond padded 128: the two-pass FP64 path (qce_wsum_f64.hip)
   QCE_BE_FAST,         // fp16-split / FP32-MFMA kernels (QCE_KERNEL picks between them per launch)
   QCE_BE_INT8,         // int8 digit planes on the i8 MFMA, quantised observations, padded <= 64 (k_est_all_i8)
+  QCE_BE_FOURIER_PILOTS,  // (block-)circulant mixture, A = kron(x, I_N): per-bin P x P tables (qce_fft_pilot.hip)
 };
+// the Fourier-domain families: per-bin tables are the active ones, the dense tables are computed on demand
+inline bool qce_be_fourier(QceBackend be) { return be == QCE_BE_FOURIER || be == QCE_BE_FOURIER_PILOTS; }
 
 struct qce_model {
   int K = 0, N = 0, device = 0;
@@ -61,6 +64,7 @@ struct qce_model {
   int beta_first = 0;  // QCE_OPT_BETA_FIRST: multi-bit Cr mixes with the first gain (blmmse.py:53, :86)
   int precision = QCE_PRECISION_F64;  // QCE_OPT_PRECISION: arithmetic of the dense 'all' / partial path
   int int8_slices = 7;  // QCE_OPT_INT8_SLICES: digit planes per table under QCE_PRECISION_INT8
+  int fourier_pilots = 0;  // QCE_OPT_FOURIER_PILOTS: A = kron(x, I_N) on a structured model takes the Fourier family
   hipStream_t stream = nullptr;
   int has_mean = 0;
   std::vector<double> weights;
@@ -125,6 +129,10 @@ struct qce_model {
   DevBuf<int> f_bad;
   DevBuf<double> f_pr, f_pur, f_pui, f_pc, f_pw, f_pbr, f_pbi;  // qce_fft_mfma.hip tables
   int fft_mfma = 0;                                            // the MFMA kernel serves 'all' / partial
+  // ... with pilots, A = kron(x, I_N) (qce_fft_pilot.hip): pilot count and vector of the last such prepare, tables
+  int fp_P = 0;
+  double2 fp_x[4] = {};
+  DevBuf<double> fp_tabL, fp_tabW, fp_cprime;
   // host-I/O pipeline of qce_estimate: two pinned slots per direction, copy-in / copy-out streams
   struct {
     double2* pin_y[2] = {nullptr, nullptr};
@@ -138,6 +146,7 @@ struct qce_model {
     int M = 0, quant_kind = 0, n_levels = 0;
     double snr_db = 0.0, n_bits = 1.0;
     std::vector<double> thr, lab;
+    std::vector<double> A;  // the observation matrix of a prepare onto QCE_BE_FOURIER_PILOTS (interleaved complex)
   } last;
 };
 

@@ -148,7 +148,7 @@ class Gmm_nbit:
     (K,N) and ``covs_cplx`` (K,N,N) the channel-domain model.
     """
 
-    def __init__(self, *gmm_args, device=0, precision="f64", **gmm_kwargs):
+    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, **gmm_kwargs):
         if _SkGaussianMixture is not None:
             self.gm = _GaussianMixtureState(*gmm_args, **gmm_kwargs)
         else:
@@ -166,6 +166,9 @@ class Gmm_nbit:
         # int8_slices digit planes of the tables on the i8 MFMA for quantised observations (opt-in; FP64 elsewhere)
         self.precision = precision
         self.int8_slices = 7
+        # opt-in: a (block-)circulant model observed through A = kron(x, I_N), 2..4 pilots, is estimated per DFT bin
+        # (P x P blocks) instead of densely at M = P N
+        self.fourier_pilots = bool(fourier_pilots)
         self.mirror_state = True
         self._dev = None
         self._dev_key = None
@@ -187,9 +190,11 @@ class Gmm_nbit:
         return obj
 
     @classmethod
-    def from_params(cls, means_cplx, covs_cplx, weights, covariance_type="full", device=0, precision="f64"):
+    def from_params(cls, means_cplx, covs_cplx, weights, covariance_type="full", device=0, precision="f64",
+                    fourier_pilots=False):
         covs = np.asarray(covs_cplx, dtype=complex)
-        obj = cls(n_components=covs.shape[0], covariance_type=covariance_type, device=device, precision=precision)
+        obj = cls(n_components=covs.shape[0], covariance_type=covariance_type, device=device, precision=precision,
+                  fourier_pilots=fourier_pilots)
         obj.means_cplx = np.zeros(covs.shape[:2], complex) if means_cplx is None else np.asarray(means_cplx, complex)
         obj.covs_cplx = covs
         obj.gm.weights_ = np.asarray(weights, dtype=float)
@@ -312,11 +317,14 @@ class Gmm_nbit:
         w = np.asarray(self.gm.weights_, dtype=float)
         precision = getattr(self, "precision", "f64")
         slices = int(getattr(self, "int8_slices", 7)) if precision == "int8" else None
-        key = (self._param_digest(covs, means, w), self.device, precision, slices)
+        pilots = bool(getattr(self, "fourier_pilots", False))  # getattr: objects pickled before the option existed
+        key = (self._param_digest(covs, means, w), self.device, precision, slices, pilots)
         if self._dev is None or self._dev_key != key:
             self._dev = _lib.DeviceModel(means, covs, w, device=self.device)
             if precision != "f64":
                 self._dev.set_precision(precision, **({} if slices is None else {"slices": slices}))
+            if pilots:
+                self._dev.set_fourier_pilots(True)
             self._dev_key = key
             self._state = None
         return self._dev
@@ -468,8 +476,8 @@ class Gmm_quant(Gmm_nbit):
     branch (:300-327): inf goes through the uniform-quantiser gain, which is the identity, so the
     result is the same; with a Lloyd quantiser the reference overflows, which is mirrored."""
 
-    def __init__(self, *gmm_args, device=0, precision="f64", **gmm_kwargs):
-        super().__init__(*gmm_args, device=device, precision=precision, **gmm_kwargs)
+    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, **gmm_kwargs):
+        super().__init__(*gmm_args, device=device, precision=precision, fourier_pilots=fourier_pilots, **gmm_kwargs)
         self.quantizer = None
         self.sigma2 = None
         self.n_bits = None
