@@ -257,6 +257,23 @@ int qce_quant_moments(const double* X, int64_t B, int N, int K, const double* re
                       const double* thresholds, int T, double* nk_out, double* corr_out, double* probs_out,
                       int device, int io, void* stream);
 
+/* Lloyd's k-means as sklearn's `_kmeans_single_lloyd` runs it (dense data, unit weights): the K-means initialisation
+ * of the fits (gmm_cplx_bussgang.py:546-551) without the host.  X (B,N) c128 is clustered as (B, D = 2N) doubles in
+ * its stored interleaved order (re0, im0, re1, ...); x_mean (D, NULL = zero) is subtracted from every row as it is
+ * loaded.  centers_init / centers_out (K, D): centred, in the same interleaved column order.  The loop stops when no
+ * label changed ("strict"), else when the squared centre shift is <= tol_abs, else after max_iter (>= 1) iterations;
+ * after a stop that was not strict the rows are assigned once more to the final centres.  Empty clusters take the rows
+ * farthest from their centres (`_relocate_empty_clusters_dense`: ascending cluster index, descending distance).
+ * labels_out (B,) int64; resp_out (B,K) f64 one-hot (NULL: not wanted);
+ * info_out[4] = {n_iter, inertia (sum_b |x_b - c_label(b)|^2), strict (0 / 1), relocated rows}.
+ * X / labels_out / resp_out where `io` says; x_mean, both centre arrays and info_out are host memory.
+ * 1 <= N <= 256, 1 <= K <= 1024 (beyond: QCE_ENOTIMPL); K > B: QCE_EARG.  Model-free; `stream` NULL = the null stream
+ * of `device`; the call returns when the results are written.  Deterministic: no floating-point atomics, fixed
+ * summation order. */
+int qce_kmeans_lloyd(const double* X, int64_t B, int N, int K, const double* x_mean, const double* centers_init,
+                     int max_iter, double tol_abs, double* centers_out, int64_t* labels_out, double* resp_out,
+                     double* info_out, int device, int io, void* stream);
+
 /* Set a model option (QCE_OPT_*); drops the prepared state. */
 int qce_model_set_option(qce_model* model, int option, double value);
 

@@ -12,13 +12,16 @@ arithmetic of every iteration runs in libqce.so:
 
 Training data and responsibilities stay resident on the device for the whole fit (torch tensors
 as plain device buffers).  The K-means initialisation is sklearn's, on the host, as in the
-reference (:546-551) — same estimator, same random_state stream, so the same initial labels.
+reference (:546-551) — same estimator, same random_state stream, so the same initial labels.  With
+``kmeans="device"`` the seeds are still sklearn's, from the same stream, and the Lloyd loop runs on the
+resident data (kmeans.py): the same labels, handed to the first M-step as a device tensor.
 """
 import warnings
 
 import numpy as np
 
 from . import _lib
+from .kmeans import DeviceKMeans, check_kmeans_option
 
 
 def _torch():
@@ -208,7 +211,11 @@ def _initialize_parameters(obj, em, X, random_state):
     """:538-556 then _initialize (:558-590)."""
     gm = obj.gm
     n_samples = X.shape[0]
-    if gm.init_params == "kmeans":
+    if gm.init_params == "kmeans" and check_kmeans_option(getattr(obj, "kmeans", "host")) == "device":
+        # the same seeds from the same stream; the Lloyd loop on em.X, the one-hot responsibilities stay on the device
+        resp = DeviceKMeans(gm.n_components, n_init=1, random_state=random_state, device=obj.device)._fit(
+            em.X, host=X, want_resp=True).resp_
+    elif gm.init_params == "kmeans":
         from sklearn import cluster
         resp = np.zeros((n_samples, gm.n_components))
         X_real = np.concatenate([X.real, X.imag], axis=1)  # ut.cplx2real(X, axis=1), utils.py:504-508

@@ -28,6 +28,7 @@ import numpy as np
 from scipy.special import erf
 
 from . import _em, _lib, covrec
+from .kmeans import DeviceKMeans, check_kmeans_option
 from .rate import quantized_variance
 
 
@@ -228,6 +229,12 @@ class DeviceBackend:
         _, corr, probs = covrec.quant_moments(self.em.X, R, means, self.quantizer[0], device=self.device)
         return corr, probs
 
+    def kmeans_resp(self, X, K, random_state):
+        """One-hot (B, K) responsibilities of the K-means initialisation as a device tensor: sklearn's seeds, the
+        Lloyd loop on the resident observations (kmeans.DeviceKMeans).  X: the host copy of em.X."""
+        return DeviceKMeans(K, n_init=1, random_state=random_state, device=self.device)._fit(
+            self.em.X, host=X, want_resp=True).resp_
+
     def gains(self, covs):
         """Bussgang gains of Cy_k = covs_k + sigma2 I (get_Bussgang_matrix of uniform_quantizer.py:60-72 /
         lloyd_max_quantizer.py:10-21) from the prepare kernels (A = I: A_eff = diag gain)."""
@@ -294,7 +301,9 @@ def fit_predict(obj, X, backend=None):
     try:
         for init in range(n_init):
             if do_init:  # _initialize_parameters / _initialize (:575-638)
-                if gm.init_params == "kmeans":
+                if gm.init_params == "kmeans" and check_kmeans_option(getattr(obj, "kmeans", "host")) == "device":
+                    resp = be.kmeans_resp(X, K, random_state)  # a device tensor: the M-step and moments take it
+                elif gm.init_params == "kmeans":
                     from sklearn import cluster
                     resp = np.zeros((n_samples, K))
                     label = cluster.KMeans(n_clusters=K, n_init=1, random_state=random_state).fit(

@@ -19,6 +19,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from .kmeans import check_kmeans_option
 
 try:  # the reference keeps its hyper-parameters and fitted weights in an sklearn object (:86-87)
     from sklearn.mixture import GaussianMixture as _SkGaussianMixture
@@ -148,7 +149,7 @@ class Gmm_nbit:
     (K,N) and ``covs_cplx`` (K,N,N) the channel-domain model.
     """
 
-    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, **gmm_kwargs):
+    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, kmeans="host", **gmm_kwargs):
         if _SkGaussianMixture is not None:
             self.gm = _GaussianMixtureState(*gmm_args, **gmm_kwargs)
         else:
@@ -169,6 +170,9 @@ class Gmm_nbit:
         # opt-in: a (block-)circulant model observed through A = kron(x, I_N), 2..4 pilots, is estimated per DFT bin
         # (P x P blocks) instead of densely at M = P N
         self.fourier_pilots = bool(fourier_pilots)
+        # K-means initialisation of fit: "host" = sklearn's KMeans as in the reference (the default), "device" = the
+        # same seeds and the Lloyd loop on the resident training data (kmeans.DeviceKMeans; opt-in)
+        self.kmeans = check_kmeans_option(kmeans)
         self.mirror_state = True
         self._dev = None
         self._dev_key = None
@@ -176,11 +180,12 @@ class Gmm_nbit:
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def from_reference(cls, ref, device=0):
+    def from_reference(cls, ref, device=0, kmeans=None):
         """Adopt a fitted reference ``Gmm_nbit``/``Gmm_quant`` (e.g. a joblib-loaded object,
-        Bussgang_GMM.py:270-278): reads means_cplx, covs_cplx and the sklearn parameter bag."""
+        Bussgang_GMM.py:270-278): reads means_cplx, covs_cplx and the sklearn parameter bag.  kmeans: the option of
+        later fits (None: the one `ref` carries, else "host")."""
         obj = cls.__new__(cls)
-        Gmm_nbit.__init__(obj, device=device)
+        Gmm_nbit.__init__(obj, device=device, kmeans=getattr(ref, "kmeans", "host") if kmeans is None else kmeans)
         obj.gm = copy.deepcopy(ref.gm)
         if _GaussianMixtureState is not None and type(obj.gm) is _SkGaussianMixture:
             obj.gm.__class__ = _GaussianMixtureState
@@ -476,8 +481,9 @@ class Gmm_quant(Gmm_nbit):
     branch (:300-327): inf goes through the uniform-quantiser gain, which is the identity, so the
     result is the same; with a Lloyd quantiser the reference overflows, which is mirrored."""
 
-    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, **gmm_kwargs):
-        super().__init__(*gmm_args, device=device, precision=precision, fourier_pilots=fourier_pilots, **gmm_kwargs)
+    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, kmeans="host", **gmm_kwargs):
+        super().__init__(*gmm_args, device=device, precision=precision, fourier_pilots=fourier_pilots, kmeans=kmeans,
+                         **gmm_kwargs)
         self.quantizer = None
         self.sigma2 = None
         self.n_bits = None

@@ -30,6 +30,7 @@ global RNG in the same order, so a seeded global RNG gives the reference's initi
 import numpy as np
 
 from .gmm import Gmm_nbit
+from .kmeans import DeviceKMeans, check_kmeans_option
 
 EPS10 = 10.0 * np.finfo(np.float64).eps  # qce_em_mstep adds it to nk (sklearn's M-step, gmm :721)
 
@@ -96,7 +97,7 @@ def mfa_em(init, stats, maxiter, tol, zero_mean, PPCA=False, lock_psis=False, n_
 
 class Mofa:
     def __init__(self, n_components, latent_dim, PPCA=False, lock_psis=False, rs_clip=0.0,
-                 max_condition_number=1.e6, maxiter=100, tol=1e-6, verbose=True, device=0):
+                 max_condition_number=1.e6, maxiter=100, tol=1e-6, verbose=True, device=0, kmeans="host"):
         self.n_components = n_components
         self.M = latent_dim
         self.PPCA = PPCA
@@ -107,6 +108,7 @@ class Mofa:
         self.verbose = verbose
         self.max_condition_number = float(max_condition_number)
         self.device = device
+        self.kmeans = check_kmeans_option(kmeans)  # "host": sklearn's KMeans (the default); "device": kmeans.DeviceKMeans
         self.means = self.covs = self.lambdas = self.psis = self.amps = None
         self.inv_covs = None
         self.zero_mean = False
@@ -114,10 +116,11 @@ class Mofa:
         self._core = None
 
     @classmethod
-    def from_reference(cls, ref, device=0):
+    def from_reference(cls, ref, device=0, kmeans=None):
         """Adopt a fitted reference ``Mofa`` (e.g. a joblib-loaded object): reads means, covs, amps,
-        lambdas, psis."""
-        obj = cls(ref.n_components, ref.M, device=device)
+        lambdas, psis.  kmeans: the option of later fits (None: the one `ref` carries, else "host")."""
+        obj = cls(ref.n_components, ref.M, device=device,
+                  kmeans=getattr(ref, "kmeans", "host") if kmeans is None else kmeans)
         for name in ("means", "covs", "amps", "lambdas", "psis", "zero_mean", "D"):
             setattr(obj, name, np.copy(getattr(ref, name)) if isinstance(getattr(ref, name, None), np.ndarray)
                     else getattr(ref, name, None))
@@ -143,9 +146,12 @@ class Mofa:
     def _initialize(self, data):
         """_initialize (:219-241): K-means centres (sklearn, numpy's global RNG), random factor loadings,
         per-dimension data variance, random amplitudes -- the reference's draws in its order."""
-        from sklearn import cluster
         K, D, M = self.n_components, data.shape[1], self.M
-        km = cluster.KMeans(n_clusters=K, n_init=1).fit(np.concatenate([data.real, data.imag], axis=1))
+        if check_kmeans_option(getattr(self, "kmeans", "host")) == "device":
+            km = DeviceKMeans(K, n_init=1, device=self.device).fit(data)  # numpy's global RNG, as below
+        else:
+            from sklearn import cluster
+            km = cluster.KMeans(n_clusters=K, n_init=1).fit(np.concatenate([data.real, data.imag], axis=1))
         re, im = np.split(km.cluster_centers_, 2, axis=1)
         means = re + 1j * im
         if self.zero_mean:
