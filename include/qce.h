@@ -274,6 +274,25 @@ int qce_kmeans_lloyd(const double* X, int64_t B, int N, int K, const double* x_m
                      int max_iter, double tol_abs, double* centers_out, int64_t* labels_out, double* resp_out,
                      double* info_out, int device, int io, void* stream);
 
+/* k-means++ seeding as sklearn's `_kmeans_plusplus` runs it (dense data, unit weights), from random numbers drawn in
+ * advance: all its draws are independent of the data (one `choice` for the first centre, `uniform(size=n_trials)` per
+ * further centre), so the host draws them in sklearn's order and every step runs on the device.  X and x_mean as for
+ * qce_kmeans_lloyd.  first: the row of the first centre.  u (K-1, n_trials), host, each in [0, 1) (NULL allowed when
+ * K = 1): for centre c >= 1 the candidates are the first rows whose inclusive cumulative sum of closest[b] (the squared
+ * distance to the nearest centre so far) reaches u[c-1][t] * pot (`np.searchsorted`, side "left"; clipped to B - 1),
+ * and the candidate with the first smallest new potential becomes the centre (`np.argmin`).  Distances are taken in
+ * the difference form.
+ * indices_out (K,) int64 the chosen rows; centers_out (K, D) = X[indices] - x_mean (one subtraction per element),
+ * centred and interleaved; cand_out (K-1, n_trials) int64 the candidate rows (NULL: not wanted); pot_out (K,) the
+ * potential after each centre (NULL: not wanted).  X where `io` says; every other buffer is host memory.
+ * 1 <= N <= 256, 1 <= K <= 1024, 1 <= n_trials <= 16 (beyond: QCE_ENOTIMPL); K > B, `first` outside [0, B) or a u
+ * outside [0, 1): QCE_EARG.  Model-free; `stream` NULL = the null stream of `device`; all steps are enqueued and the
+ * call returns when the results are written.  Deterministic: no floating-point atomics, fixed summation order
+ * (csrc/qce_kmeans_seed.hip). */
+int qce_kmeans_seed(const double* X, int64_t B, int N, int K, const double* x_mean, int64_t first, const double* u,
+                    int n_trials, int64_t* indices_out, double* centers_out, int64_t* cand_out, double* pot_out,
+                    int device, int io, void* stream);
+
 /* Set a model option (QCE_OPT_*); drops the prepared state. */
 int qce_model_set_option(qce_model* model, int option, double value);
 

@@ -14,14 +14,15 @@ Training data and responsibilities stay resident on the device for the whole fit
 as plain device buffers).  The K-means initialisation is sklearn's, on the host, as in the
 reference (:546-551) — same estimator, same random_state stream, so the same initial labels.  With
 ``kmeans="device"`` the seeds are still sklearn's, from the same stream, and the Lloyd loop runs on the
-resident data (kmeans.py): the same labels, handed to the first M-step as a device tensor.
+resident data (kmeans.py; with ``kmeans="device-seeded"`` the same seeds are chosen on the device as
+well): the same labels, handed to the first M-step as a device tensor.
 """
 import warnings
 
 import numpy as np
 
 from . import _lib
-from .kmeans import DeviceKMeans, check_kmeans_option
+from .kmeans import DEVICE_OPTIONS, DeviceKMeans, check_kmeans_option, seeding_of
 
 
 def _torch():
@@ -211,10 +212,12 @@ def _initialize_parameters(obj, em, X, random_state):
     """:538-556 then _initialize (:558-590)."""
     gm = obj.gm
     n_samples = X.shape[0]
-    if gm.init_params == "kmeans" and check_kmeans_option(getattr(obj, "kmeans", "host")) == "device":
-        # the same seeds from the same stream; the Lloyd loop on em.X, the one-hot responsibilities stay on the device
-        resp = DeviceKMeans(gm.n_components, n_init=1, random_state=random_state, device=obj.device)._fit(
-            em.X, host=X, want_resp=True).resp_
+    option = check_kmeans_option(getattr(obj, "kmeans", "host"))
+    if gm.init_params == "kmeans" and option in DEVICE_OPTIONS:
+        # the same seeds from the same stream ("device-seeded": chosen on the device too); the Lloyd loop on em.X, the
+        # one-hot responsibilities stay on the device
+        resp = DeviceKMeans(gm.n_components, n_init=1, random_state=random_state, device=obj.device,
+                            seeding=seeding_of(option))._fit(em.X, host=X, want_resp=True).resp_
     elif gm.init_params == "kmeans":
         from sklearn import cluster
         resp = np.zeros((n_samples, gm.n_components))

@@ -28,7 +28,7 @@ import numpy as np
 from scipy.special import erf
 
 from . import _em, _lib, covrec
-from .kmeans import DeviceKMeans, check_kmeans_option
+from .kmeans import DEVICE_OPTIONS, DeviceKMeans, check_kmeans_option, seeding_of
 from .rate import quantized_variance
 
 
@@ -229,10 +229,11 @@ class DeviceBackend:
         _, corr, probs = covrec.quant_moments(self.em.X, R, means, self.quantizer[0], device=self.device)
         return corr, probs
 
-    def kmeans_resp(self, X, K, random_state):
-        """One-hot (B, K) responsibilities of the K-means initialisation as a device tensor: sklearn's seeds, the
-        Lloyd loop on the resident observations (kmeans.DeviceKMeans).  X: the host copy of em.X."""
-        return DeviceKMeans(K, n_init=1, random_state=random_state, device=self.device)._fit(
+    def kmeans_resp(self, X, K, random_state, seeding="host"):
+        """One-hot (B, K) responsibilities of the K-means initialisation as a device tensor: sklearn's seeds (chosen
+        on the host, or with seeding="device" on the device), the Lloyd loop on the resident observations
+        (kmeans.DeviceKMeans).  X: the host copy of em.X."""
+        return DeviceKMeans(K, n_init=1, random_state=random_state, device=self.device, seeding=seeding)._fit(
             self.em.X, host=X, want_resp=True).resp_
 
     def gains(self, covs):
@@ -301,8 +302,10 @@ def fit_predict(obj, X, backend=None):
     try:
         for init in range(n_init):
             if do_init:  # _initialize_parameters / _initialize (:575-638)
-                if gm.init_params == "kmeans" and check_kmeans_option(getattr(obj, "kmeans", "host")) == "device":
-                    resp = be.kmeans_resp(X, K, random_state)  # a device tensor: the M-step and moments take it
+                option = check_kmeans_option(getattr(obj, "kmeans", "host"))
+                if gm.init_params == "kmeans" and option in DEVICE_OPTIONS:
+                    # a device tensor: the M-step and moments take it
+                    resp = be.kmeans_resp(X, K, random_state, seeding=seeding_of(option))
                 elif gm.init_params == "kmeans":
                     from sklearn import cluster
                     resp = np.zeros((n_samples, K))

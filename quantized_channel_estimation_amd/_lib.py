@@ -107,6 +107,8 @@ SIGNATURES = {
                                          _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qce_kmeans_lloyd": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                         ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "qce_kmeans_seed": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64, _vp,
+                                       ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qce_model_structure": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                            ctypes.POINTER(ctypes.c_int)]),
     # K-shard over a communicator (csrc/qce_kshard.hip)

@@ -42,3 +42,28 @@ hipError_t qce_launch_km_rowdist(const QceKmPlan& p, const double* X, const doub
 hipError_t qce_launch_km_vsum(long long n, const double* v, double* out, hipStream_t st);
 // resp (B, K): 1.0 at the label, 0.0 elsewhere
 hipError_t qce_launch_km_onehot(const QceKmPlan& p, const long long* labels, double* resp, hipStream_t st);
+
+// k-means++ seeding from pre-drawn uniforms (qce_kmeans_seed.hip).  closest[b] lives in a row of a (T, stride) scratch
+// buffer, stride = C * chunk >= B (rows past B hold zeros), with (T, C) per-chunk partial sums beside it.
+struct QceKmSeedPlan {
+  long long B = 0;
+  int N = 0, NP = 0;     // complex elements per row, rounded up to 64
+  long long chunk = 0;   // rows per chunk (a multiple of 64), one candidate-pass workgroup each
+  int C = 0;             // chunks (<= 1024)
+  long long stride = 0;  // C * chunk
+};
+QceKmSeedPlan qce_km_seed_plan(long long B, int N);
+// out (T, stride), part (T, C): min(closest, |x_b - x_cand[t]|^2) and its chunk sums, 1 <= T <= 16; closest = row
+// win[0] of the scratch buffer `closest` (NULL: +inf, the pass of the first centre, `win` unused)
+hipError_t qce_launch_km_seed_cand(const QceKmSeedPlan& p, int T, const double* X, const double* mean,
+                                   const long long* cand, const double* closest, const int* win, double* out,
+                                   double* part, hipStream_t st);
+// From the last pass (part, scratch, cand_prev; Tprev rows): idx_out[0], pot_out[0], win_out[0] = the candidate with
+// the first smallest potential, that potential and its scratch row; cand_next[t] = the first row whose inclusive
+// cumulative sum of that scratch row is >= u[t] * pot, clipped to B - 1, for t < Tn (Tn = 0: no search)
+hipError_t qce_launch_km_seed_pick(const QceKmSeedPlan& p, int Tprev, const double* part, const double* scratch,
+                                   const long long* cand_prev, const double* u, int Tn, long long* idx_out,
+                                   double* pot_out, int* win_out, long long* cand_next, hipStream_t st);
+// centers (K, 2N) = X[idx[k]] - mean
+hipError_t qce_launch_km_seed_gather(const QceKmSeedPlan& p, int K, const double* X, const double* mean,
+                                     const long long* idx, double* centers, hipStream_t st);

@@ -171,7 +171,8 @@ class Gmm_nbit:
         # (P x P blocks) instead of densely at M = P N
         self.fourier_pilots = bool(fourier_pilots)
         # K-means initialisation of fit: "host" = sklearn's KMeans as in the reference (the default), "device" = the
-        # same seeds and the Lloyd loop on the resident training data (kmeans.DeviceKMeans; opt-in)
+        # same seeds and the Lloyd loop on the resident training data (kmeans.DeviceKMeans; opt-in), "device-seeded"
+        # = the same, with the k-means++ seeds chosen on the device from pre-drawn uniforms (opt-in)
         self.kmeans = check_kmeans_option(kmeans)
         self.mirror_state = True
         self._dev = None

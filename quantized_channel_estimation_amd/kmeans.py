@@ -5,7 +5,9 @@ csrc/qce_kmeans.hip).
 complex rows.  The host part is sklearn's own: the data are centred with their column mean, ``tol`` is scaled
 by the mean column variance, and the seeds come from the public ``sklearn.cluster.kmeans_plusplus`` with the
 caller's ``RandomState`` -- the same seeds, and the same stream afterwards, as ``KMeans(n_init=1,
-random_state=rs).fit``.  Only the Lloyd iterations move: they run on the resident complex128 rows in their stored
+random_state=rs).fit``.  With ``seeding="device"`` the same seeds are chosen on the device instead
+(``qce_kmeans_seed``, csrc/qce_kmeans_seed.hip) from random numbers drawn in advance in sklearn's order
+(``predraw``).  Otherwise only the Lloyd iterations move: they run on the resident complex128 rows in their stored
 interleaved order (distances do not depend on the column order); centres are converted to and from sklearn's
 ``[Re | Im]`` column order here.
 """
@@ -13,14 +15,21 @@ import numpy as np
 
 from . import _lib
 
-KMEANS_OPTIONS = ("host", "device")
+KMEANS_OPTIONS = ("host", "device", "device-seeded")
+DEVICE_OPTIONS = ("device", "device-seeded")  # the settings that cluster the resident data
 
 
 def check_kmeans_option(value):
-    """The ``kmeans=`` keyword of the fits: "host" (sklearn's KMeans, the default) or "device"."""
+    """The ``kmeans=`` keyword of the fits: "host" (sklearn's KMeans, the default), "device" (host seeds, the Lloyd
+    loop on the device) or "device-seeded" (the k-means++ seeds chosen on the device as well)."""
     if value not in KMEANS_OPTIONS:
-        raise ValueError(f"kmeans must be 'host' or 'device', not {value!r}")
+        raise ValueError(f"kmeans must be 'host', 'device' or 'device-seeded', not {value!r}")
     return value
+
+
+def seeding_of(option):
+    """The ``seeding=`` of DeviceKMeans that a fit's ``kmeans=`` option stands for."""
+    return "device" if option == "device-seeded" else "host"
 
 
 def _is_tensor(a):
@@ -77,6 +86,57 @@ def lloyd_device(X, centers_init, tol_abs, max_iter, x_mean=None, want_resp=Fals
                 strict=bool(info[2]), relocated=int(info[3]), resp=resp)
 
 
+def predraw(random_state, B, K, n_local_trials=None):
+    """Every random number ``sklearn.cluster.kmeans_plusplus(X (B rows), K, random_state=...)`` draws, in its order:
+    ``(first, U)`` with ``first`` the row of the first centre and ``U`` (K - 1, T) the uniforms of the further
+    centres, T = 2 + int(log K) unless given.  None of the draws depends on the data, so ``random_state`` is left in
+    the state ``kmeans_plusplus`` leaves it in.
+
+    Pinned to ``_kmeans_plusplus`` of the installed scikit-learn 1.7.2: one ``choice(B, p=ones / B)``, then
+    ``uniform(size=T)`` once per further centre (tests/test_kmeans_seed_ref.py compares the states)."""
+    B, K = int(B), int(K)
+    T = 2 + int(np.log(K)) if n_local_trials is None else int(n_local_trials)
+    first = int(random_state.choice(B, p=np.full(B, 1.0 / B)))
+    U = np.empty((K - 1, T))
+    for c in range(K - 1):
+        U[c] = random_state.uniform(size=T)
+    return first, U
+
+
+def seed_device(X, K, first, U, x_mean=None, device=0, want_debug=False):
+    """k-means++ seeds chosen on the device from pre-drawn uniforms (``qce_kmeans_seed``).
+
+    X: (B, N) complex128 NumPy array (uploaded) or tensor on ``device`` (used in place); ``first`` and ``U`` (K - 1, T)
+    from ``predraw``; x_mean (2N,) interleaved or None.  Returns (centers (K, 2N) centred and interleaved, indices (K,)
+    int64), and with want_debug also (candidates (K - 1, T) int64, potentials (K,))."""
+    import torch
+    dev = torch.device("cuda", int(device))
+    if not _is_tensor(X):
+        X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.complex128)).to(dev)
+    elif X.device != dev or X.dtype != torch.complex128:
+        raise ValueError(f"X must be a complex128 tensor on {dev}")
+    X = X.contiguous()
+    if X.dim() != 2:
+        raise ValueError("X must be (n_samples, n_features)")
+    B, N = X.shape
+    K = int(K)
+    U = np.ascontiguousarray(U, dtype=np.float64)
+    if U.ndim != 2 or U.shape[0] != max(K - 1, 0) or U.shape[1] < 1:
+        raise ValueError(f"U must be ({K - 1}, n_trials)")
+    T = U.shape[1]
+    mean = None if x_mean is None else np.ascontiguousarray(x_mean, dtype=np.float64).reshape(2 * N)
+    centers = np.empty((max(K, 0), 2 * N))
+    indices = np.empty(max(K, 0), dtype=np.int64)
+    cand = np.empty((max(K - 1, 0), T), dtype=np.int64) if want_debug else None
+    pot = np.empty(max(K, 0)) if want_debug else None
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(_lib.load().qce_kmeans_seed(_lib.ptr(X), B, N, K, _lib.ptr(mean), int(first),
+                                           _lib.ptr(U) if K > 1 else None, T, _lib.ptr(indices), _lib.ptr(centers),
+                                           _lib.ptr(cand), _lib.ptr(pot), int(device), _lib.IO_DEVICE,
+                                           stream.cuda_stream))
+    return (centers, indices, cand, pot) if want_debug else (centers, indices)
+
+
 def _same_clustering(a, b, K):
     """sklearn's _is_same_clustering: equal up to a permutation of the labels."""
     mapping = np.full(K, -1, dtype=np.int64)
@@ -94,11 +154,19 @@ class DeviceKMeans:
     fit(X): X (B, N) complex NumPy array, or a complex128 tensor already resident on ``device`` (not uploaded
     again).  Sets ``labels_``, ``cluster_centers_`` ((K, 2N) in sklearn's ``[Re | Im]`` order, mean added back),
     ``inertia_`` and ``n_iter_``.  init: "k-means++", "random" or a (K, 2N) array in sklearn's column order.
+    seeding: "host" (``sklearn.cluster.kmeans_plusplus``, the default) or "device": with init="k-means++" the random
+    numbers are drawn in advance (``predraw``) and the seeds are chosen on the device (``seed_device``), once per
+    ``n_init`` run; any other init ignores it.
     ``_lloyd``: a callable (X_centred (B, 2N), centers_init (K, 2N), tol_abs, max_iter) -> (labels, centers, inertia,
-    n_iter, ...) in sklearn's column order that stands in for the device loop (CPU tests)."""
+    n_iter, ...) in sklearn's column order that stands in for the device loop (CPU tests).  ``_seed``: a callable
+    (X_centred (B, 2N), K, first, U) -> (indices, ...) that stands in for the device seeding (CPU tests)."""
 
     def __init__(self, n_clusters, init="k-means++", n_init=1, max_iter=300, tol=1e-4, random_state=None, device=0,
-                 _lloyd=None):
+                 seeding="host", _lloyd=None, _seed=None):
+        if seeding not in ("host", "device"):
+            raise ValueError(f"seeding must be 'host' or 'device', not {seeding!r}")
+        self.seeding = seeding
+        self._seed = _seed
         self.n_clusters = int(n_clusters)
         self.init = init
         self.n_init = int(n_init)
@@ -143,7 +211,8 @@ class DeviceKMeans:
         Xc -= mean
         if init_is_array:
             init -= mean
-        if self._lloyd is None:
+        seed_on_device = self.seeding == "device" and not init_is_array and init == "k-means++"
+        if self._lloyd is None or (seed_on_device and self._seed is None):
             if Xd is None:
                 import torch
                 Xd = torch.from_numpy(np.ascontiguousarray(Xh, dtype=np.complex128)).to(
@@ -153,6 +222,12 @@ class DeviceKMeans:
         for _ in range(self.n_init):
             if init_is_array:
                 C0 = init
+            elif seed_on_device:
+                first, U = predraw(rs, B, K)  # the stream moves on as kmeans_plusplus would move it
+                if self._seed is not None:
+                    C0 = Xc[np.asarray(self._seed(Xc, K, first, U)[0])]
+                else:
+                    C0 = from_interleaved(seed_device(Xd, K, first, U, x_mean=mean_il, device=self.device)[0])
             elif init == "k-means++":
                 from sklearn.cluster import kmeans_plusplus
                 C0, _idx = kmeans_plusplus(Xc, K, random_state=rs)

@@ -30,7 +30,7 @@ global RNG in the same order, so a seeded global RNG gives the reference's initi
 import numpy as np
 
 from .gmm import Gmm_nbit
-from .kmeans import DeviceKMeans, check_kmeans_option
+from .kmeans import DEVICE_OPTIONS, DeviceKMeans, check_kmeans_option, seeding_of
 
 EPS10 = 10.0 * np.finfo(np.float64).eps  # qce_em_mstep adds it to nk (sklearn's M-step, gmm :721)
 
@@ -108,7 +108,8 @@ class Mofa:
         self.verbose = verbose
         self.max_condition_number = float(max_condition_number)
         self.device = device
-        self.kmeans = check_kmeans_option(kmeans)  # "host": sklearn's KMeans (the default); "device": kmeans.DeviceKMeans
+        # "host": sklearn's KMeans (the default); "device" / "device-seeded": kmeans.DeviceKMeans
+        self.kmeans = check_kmeans_option(kmeans)
         self.means = self.covs = self.lambdas = self.psis = self.amps = None
         self.inv_covs = None
         self.zero_mean = False
@@ -147,8 +148,9 @@ class Mofa:
         """_initialize (:219-241): K-means centres (sklearn, numpy's global RNG), random factor loadings,
         per-dimension data variance, random amplitudes -- the reference's draws in its order."""
         K, D, M = self.n_components, data.shape[1], self.M
-        if check_kmeans_option(getattr(self, "kmeans", "host")) == "device":
-            km = DeviceKMeans(K, n_init=1, device=self.device).fit(data)  # numpy's global RNG, as below
+        option = check_kmeans_option(getattr(self, "kmeans", "host"))
+        if option in DEVICE_OPTIONS:  # numpy's global RNG, as below
+            km = DeviceKMeans(K, n_init=1, device=self.device, seeding=seeding_of(option)).fit(data)
         else:
             from sklearn import cluster
             km = cluster.KMeans(n_clusters=K, n_init=1).fit(np.concatenate([data.real, data.imag], axis=1))

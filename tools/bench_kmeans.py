@@ -9,9 +9,16 @@ fixed_ms is a one-iteration call (allocation, two assignments, the inertia).  Sh
 bytes the algorithm needs per iteration, 4 B K D flops on the FP64 MFMA and two reads of X, over that per-iteration
 time -- a whole-call rate, not a kernel's.
 
-Per K and covariance type ('full', 'circulant'), one JSON line "fit": Gmm_nbit.fit end to end with kmeans="host" and
-kmeans="device", alternating, with the time spent in the EM steps (E-step + M-step, host clock, both end
-synchronised) alongside.  Lines go to stdout and to --out."""
+Per K, one JSON line "seed": the k-means++ seeding alone, sklearn.cluster.kmeans_plusplus on the centred data against
+kmeans.predraw + kmeans.seed_device (qce_kmeans_seed, csrc/qce_kmeans_seed.hip) on resident data, alternating, the
+indices compared; step_us is the device call over its K - 1 steps (two launches each: pick + search, candidate pass),
+pass_floor_us one read of X at the achievable HBM rate -- kernel times come from a kernel trace in a run of its own;
+predraw_ms the pre-drawn random numbers alone, host_part_ms what DeviceKMeans._fit does on the host before the seeding
+(real view, tolerance from the column variances, column mean, centring).
+
+Per K and covariance type ('full', 'circulant'), one JSON line "fit": Gmm_nbit.fit end to end with kmeans="host",
+kmeans="device" and kmeans="device-seeded", alternating, with the time spent in the EM steps (E-step + M-step, host
+clock, both end synchronised) alongside.  Lines go to stdout and to --out."""
 import argparse
 import json
 import os
@@ -29,6 +36,8 @@ from quantized_channel_estimation_amd import Gmm_nbit, _em, inputs, kmeans  # no
 
 FP64_PEAK = 78.6  # TFLOP/s, MI355X FP64 matrix (spec)
 HBM_PEAK = 8.0    # TB/s (spec)
+HBM_ACHIEVABLE = 6.3  # TB/s, a wide streaming copy
+FIT_OPTIONS = ("host", "device", "device-seeded")
 
 
 def make_data(B, N, seed=5):
@@ -94,8 +103,47 @@ def bench_kmeans(X, K, reps, max_iter):
             "hbm_share_of_peak": round(nbytes / t_it / (HBM_PEAK * 1e12), 4)}
 
 
+def bench_seed(X, K, reps):
+    """The seeding alone: host kmeans_plusplus against predraw + seed_device on resident data, alternating."""
+    from sklearn.cluster import kmeans_plusplus
+    B, N = X.shape
+    Xr = np.concatenate([X.real, X.imag], axis=1)
+    mean = Xr.mean(axis=0)
+    Xc = Xr - mean
+    Xd = torch.from_numpy(X).cuda()
+    mean_il = kmeans.to_interleaved(mean)
+
+    def device_seed(r):
+        first, U = kmeans.predraw(np.random.RandomState(r), B, K)
+        return kmeans.seed_device(Xd, K, first, U, x_mean=mean_il)[1]
+
+    def host_part():  # what DeviceKMeans._fit does on the host before the seeding, on the host copy of X
+        xr = np.concatenate([X.real, X.imag], axis=1).astype(np.float64, copy=False)
+        tol = float(np.mean(np.var(xr, axis=0)) * 1e-4)
+        m = xr.mean(axis=0)
+        xr -= m
+        return tol, kmeans.to_interleaved(m)
+
+    device_seed(0)  # warm-up: code objects
+    host, dev, pre, hp, same = [], [], [], [], True
+    for r in range(reps):
+        hp.append(timed(host_part)[0])
+        ms, (_, idx) = timed(lambda: kmeans_plusplus(Xc, K, random_state=np.random.RandomState(r)))
+        host.append(ms)
+        ms, didx = timed(lambda: device_seed(r))
+        dev.append(ms)
+        pre.append(timed(lambda: kmeans.predraw(np.random.RandomState(r), B, K))[0])
+        same = same and bool(np.array_equal(idx, didx))
+    nbytes = 8.0 * B * 2 * N
+    return {"what": "seed", "B": B, "N": N, "K": K, "reps": reps, "n_trials": 2 + int(np.log(K)),
+            "host_seeding_ms": spread(host), "device_seeding_ms": spread(dev), "predraw_ms": spread(pre),
+            "host_part_ms": spread(hp), "indices_equal": same, "launches_per_step": 2,
+            "step_us": round(statistics.median(dev) * 1e3 / max(K - 1, 1), 2),
+            "pass_bytes": nbytes, "pass_floor_us": round(nbytes / (HBM_ACHIEVABLE * 1e12) * 1e6, 2)}
+
+
 def bench_fit(X, K, ct, reps, em_iter):
-    """Gmm_nbit.fit with both settings, alternating; EM time from a host clock around DeviceEM.estep / mstep."""
+    """Gmm_nbit.fit with the three settings, alternating; EM time from a host clock around DeviceEM.estep / mstep."""
     clock = {"t": 0.0, "n": 0}
     estep, mstep = _em.DeviceEM.estep, _em.DeviceEM.mstep
 
@@ -112,10 +160,10 @@ def bench_fit(X, K, ct, reps, em_iter):
     out = {"what": "fit", "B": X.shape[0], "N": X.shape[1], "K": K, "covariance_type": ct, "em_max_iter": em_iter,
            "reps": reps}
     try:
-        res = {"host": [], "device": []}
-        em = {"host": [], "device": []}
-        for r in range(reps + 1):  # the first round warms both paths up and is dropped
-            for opt in ("host", "device"):
+        res = {opt: [] for opt in FIT_OPTIONS}
+        em = {opt: [] for opt in FIT_OPTIONS}
+        for r in range(reps + 1):  # the first round warms every path up and is dropped
+            for opt in FIT_OPTIONS:
                 clock["t"], clock["n"] = 0.0, 0
                 g = Gmm_nbit(n_components=K, covariance_type=ct, max_iter=em_iter, random_state=r, kmeans=opt)
                 with warnings.catch_warnings():
@@ -124,9 +172,10 @@ def bench_fit(X, K, ct, reps, em_iter):
                 if r:
                     res[opt].append(ms)
                     em[opt].append(clock["t"] * 1e3 / max(clock["n"], 1))
-        for opt in ("host", "device"):
-            out[f"fit_{opt}_ms"] = spread(res[opt])
-            out[f"em_ms_per_iter_{opt}"] = spread(em[opt])
+        for opt in FIT_OPTIONS:
+            key = opt.replace("-", "_")
+            out[f"fit_{key}_ms"] = spread(res[opt])
+            out[f"em_ms_per_iter_{key}"] = spread(em[opt])
     finally:
         _em.DeviceEM.estep, _em.DeviceEM.mstep = estep, mstep
     return out
@@ -141,7 +190,8 @@ def main():
     ap.add_argument("--max-iter", type=int, default=300)
     ap.add_argument("--em-iter", type=int, default=10)
     ap.add_argument("--no-fit", action="store_true", help="the K-means lines only (a kernel trace of the Lloyd loop)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kmeans_device", "bench.jsonl"))
+    ap.add_argument("--no-lloyd", action="store_true", help="skip the host KMeans / device Lloyd lines")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kmeans_seed", "bench.jsonl"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("bench_kmeans: no GPU visible")
@@ -154,7 +204,9 @@ def main():
             fh.flush()
 
         for K in a.K:
-            emit(bench_kmeans(X, K, a.reps, a.max_iter))
+            if not a.no_lloyd:
+                emit(bench_kmeans(X, K, a.reps, a.max_iter))
+            emit(bench_seed(X, K, a.reps))
             for ct in () if a.no_fit else ("full", "circulant"):
                 emit(bench_fit(X, K, ct, a.reps, a.em_iter))
 
