@@ -257,6 +257,39 @@ int qce_quant_moments(const double* X, int64_t B, int N, int K, const double* re
                       const double* thresholds, int T, double* nk_out, double* corr_out, double* probs_out,
                       int device, int io, void* stream);
 
+/* The per-component algebra that follows qce_quant_moments in the quantised M-step, on the device
+ * (csrc/qce_quant_recover.hip).  Both calls are model-free, take their buffers where `io` says (`thresholds` is host
+ * memory, as above; `stream` NULL = the null stream of `device`), return when the results are written, and are
+ * deterministic (no atomics, fixed order).
+ *
+ * qce_quant_variance_fit: the scalar Gauss-Newton variance fits of `est_cov_from_quant` (cov_est_quant.py:62-84 with
+ * utils.py:651-700 `gauss_newt_solve`), one per (component, dimension): probs (K,D,T,2) and nk (K,) as
+ * qce_quant_moments returns them, the T >= 1 positive ascending thresholds, the start values x0 (K,D).  p is clipped
+ * to [1/nk, (nk-1)/nk]; the 2T residuals are f = erf(t / (sqrt 2 s)) - p with J = -sqrt(2/pi) t exp(-t^2 / (2 s)) / s^2
+ * (the reference's exponent); a step is dx = -(J.f)/(J.J) (0 when J.J is exactly 0), until |dx| <= 1e-5 or 100 steps.
+ * s2_out (K,D) = max(2 s^2, 0); iters_out (K,D) int32 the steps taken.  The reference restarts a fit whose |s| is
+ * below 0.1 or above 10 from numpy's global generator: a fit that reaches either branch, or a non-finite value,
+ * stops with status_out (K,D) int32 = 1 (s2_out = 1) and is the caller's to redo; 0 otherwise.
+ *
+ * qce_herm_eig_clip: out (K,D,D) c128 = V max(L, floor) V^H + diag_post I of the Hermitian A_k = V L V^H, where A_k
+ * is C_k (K,D,D) c128 (its lower triangle is read, as eigh reads it) after the element-wise preparation `prep`:
+ * QCE_CLIP_PLAIN: C_k; QCE_CLIP_SIN: sin(pi/2 Re C_k) + j sin(pi/2 Im C_k) (the arcsine law);
+ * QCE_CLIP_SIN_SCALED: the same times sqrt(s2[k][i] s2[k][j]) (s2 (K,D) f64, else unused); then + diag_pre I.
+ * These are the clips of `estimate_gaussian_covariances_full` / `_inv` (gmm_cplx_quant.py:790-800, :819-829,
+ * :840-848, :900-920).  Parallel cyclic two-sided Jacobi, one workgroup per component with A and V in LDS; it stops
+ * when the off-diagonal Frobenius norm is <= 1e-14 ||A_k||_F.  sweeps_out (K,) int32 the sweeps taken (0: already
+ * diagonal); status_out (K,) int32 = 1 for a component still above that bound after 30 sweeps (its `out` is then not
+ * to be used), 0 otherwise.  out is exactly Hermitian.  1 <= D <= 64 (beyond: QCE_ENOTIMPL). */
+#define QCE_CLIP_PLAIN 0
+#define QCE_CLIP_SIN 1
+#define QCE_CLIP_SIN_SCALED 2
+int qce_quant_variance_fit(const double* probs, const double* nk, const double* thresholds, int T, const double* x0,
+                           int K, int D, double* s2_out, int32_t* status_out, int32_t* iters_out, int device, int io,
+                           void* stream);
+int qce_herm_eig_clip(const double* C, int K, int D, double floor, int prep, const double* s2, double diag_pre,
+                      double diag_post, double* out, int32_t* status_out, int32_t* sweeps_out, int device, int io,
+                      void* stream);
+
 /* Lloyd's k-means as sklearn's `_kmeans_single_lloyd` runs it (dense data, unit weights): the K-means initialisation
  * of the fits (gmm_cplx_bussgang.py:546-551) without the host.  X (B,N) c128 is clustered as (B, D = 2N) doubles in
  * its stored interleaved order (re0, im0, re1, ...); x_mean (D, NULL = zero) is subtracted from every row as it is

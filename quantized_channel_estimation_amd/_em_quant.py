@@ -15,7 +15,10 @@ fit matches) of d = x (zero-mean models) or d = x - mu_k (models with means, as 
 in registers: no transformed copy of the data exists on the host or the device.  The per-component Bussgang gains
 come from the prepare kernels.  The per-component K x (D x D) corrections (sin
 law, eigenvalue clipping, the scalar Gauss-Newton solves, the inverse-EM Sigma update of the Toeplitz types,
-A Cy A^H with the quantised variances) run on the host in FP64 NumPy, as in the reference.
+A Cy A^H with the quantised variances) run on the host in FP64 NumPy, as in the reference.  With
+``Gmm_quant(recovery="device")`` (opt-in) the two expensive pieces of that algebra, the variance fits and the
+eigenvalue clips, run in libqce.so as well (csrc/qce_quant_recover.hip through ``covrec.fit_variances`` and
+``covrec.eig_clip``); a variance fit that would draw a restart from NumPy's generator is handed back to the host solver.
 
 Covariance types: 'full', 'toeplitz' and 'block-toeplitz' (inverse EM) as the reference.  The reference cannot
 complete a fit of 'circulant', 'block-circulant', 'diagonal' or 'spherical' (its M-step helpers for these return
@@ -54,6 +57,25 @@ def _positive_thresholds(thresholds):
     return t[(t.shape[0] - 1) // 2 + 1:]
 
 
+def variance_fit(probs_d, nk, thres, x0):
+    """The variance fit of one dimension (cov_est_quant.py:62-84): probs_d (T, 2), thres the positive thresholds
+    repeated twice (2T,), x0 the start value.  Returns (s2_d, Gauss-Newton steps)."""
+    p = np.clip(probs_d, 1 / nk, (nk - 1) / nk)
+    p = np.concatenate((p[:, 0], p[:, 1]), axis=0)
+
+    def f(s, p=p):
+        return erf(thres / (np.sqrt(2) * s)) - p
+
+    def jac(s):
+        return -np.sqrt(2 / np.pi) * thres * np.exp(-thres ** 2 / (2 * s)) / s ** 2
+
+    x, steps = gauss_newt_solve(f, jac, np.real(x0))
+    v = x ** 2
+    if np.isnan(v):
+        v = 1.0
+    return np.clip(2 * v, 0, np.inf), steps
+
+
 def cov_from_quant(corr, probs, nk, thresholds, x0_vec):
     """est_cov_from_quant (cov_est_quant.py:31-88) from its two weighted statistics: corr = sum r s s^H / nk
     of the 1-bit signs and probs (T, 2) = sum r 1(|x_d| < t) / nk (real, imaginary part) per dimension d."""
@@ -63,20 +85,7 @@ def cov_from_quant(corr, probs, nk, thresholds, x0_vec):
     thres = np.concatenate((thres, thres), axis=0)
     s2 = np.zeros(D)
     for d in range(D):
-        p = np.clip(probs[d], 1 / nk, (nk - 1) / nk)
-        p = np.concatenate((p[:, 0], p[:, 1]), axis=0)
-
-        def f(s, p=p):
-            return erf(thres / (np.sqrt(2) * s)) - p
-
-        def jac(s):
-            return -np.sqrt(2 / np.pi) * thres * np.exp(-thres ** 2 / (2 * s)) / s ** 2
-
-        x0 = np.real(x0_vec[d])
-        v = gauss_newt_solve(f, jac, x0)[0] ** 2
-        if np.isnan(v):
-            v = 1.0
-        s2[d] = np.clip(2 * v, 0, np.inf)
+        s2[d] = variance_fit(probs[d], nk, thres, x0_vec[d])[0]
     r = np.sqrt(s2)
     return r[:, None] * corr * r[None, :]
 
@@ -87,15 +96,60 @@ def _eig_clip(c, reg):
     return (Q * w) @ Q.conj().T
 
 
-def quant_covariances(Q, nk, reg, n_bits, sigma2, quantizer, moments, gains):
+def _quantised_covariances(cov, sigma2, quantizer, gains):
+    """A Cy A^H with the quantised variances on the diagonal (:830-838), from the recovered covariances."""
+    K, D, _ = cov.shape
+    eye, idx = np.eye(D), np.arange(D)
+    cq = np.empty_like(cov)
+    A = gains(cov)
+    for k in range(K):
+        Cy = cov[k] + sigma2 * eye
+        dcr = quantized_variance(np.real(np.diag(Cy)), quantizer[0], quantizer[1])
+        c = (A[k][:, None] * Cy) * A[k][None, :].conj()
+        c[idx, idx] = dcr
+        cq[k] = c
+    return cq
+
+
+def _recovered_device(branch, Q, nk, reg, sigma2, quantizer, moments, device, x0_ones, reg_after):
+    """The recovered, clipped covariances (K, D, D) on the device, for the branch "1bit", "fits" (multi-bit) or
+    "plain" (unquantised): the variance fits (covrec.fit_variances: restarted fits are redone on the host in the host
+    path's order) and the eigenvalue clip with the element-wise steps around it fused into its load and store
+    (covrec.eig_clip).  The diagonal shifts the host applies one after the other (+ reg, - sigma2, + reg) enter as
+    one constant."""
+    K, D, _ = Q.shape
+    post = reg if reg_after else 0.0
+    if branch == "1bit":
+        return covrec.eig_clip(Q, reg, device=device, prep="sin", diag_pre=reg, diag_post=post)
+    if branch == "fits":
+        corr, probs = moments()
+        x0 = np.ones((K, D)) if x0_ones else np.real(np.einsum("kii->ki", Q)) + reg
+        s2, _ = covrec.fit_variances(probs, nk, quantizer[0], x0, device=device)
+        return covrec.eig_clip(corr, reg, device=device, prep="sin-scaled", s2=s2, diag_pre=reg - sigma2,
+                               diag_post=post)
+    return covrec.eig_clip(Q, reg, device=device, prep="plain", diag_pre=2 * reg - sigma2, diag_post=post)
+
+
+def quant_covariances(Q, nk, reg, n_bits, sigma2, quantizer, moments, gains, recovery="host", device=0):
     """estimate_gaussian_covariances_full (:773-853) from the weighted moments Q_k (K, D, D).
     moments() -> (corr (K, D, D), probs (K, D, T, 2)) for multi-bit data; gains(covs) -> (K, D) Bussgang
-    gains of Cy_k = covs_k + sigma2 I.  Returns (covariances, covariances_quant)."""
+    gains of Cy_k = covs_k + sigma2 I.  recovery "device": the variance fits and the eigenvalue clips run in
+    libqce.so (csrc/qce_quant_recover.hip).  Returns (covariances, covariances_quant)."""
     K, D, _ = Q.shape
     eye = np.eye(D)
     cov = np.empty_like(Q)
     cq = np.array(Q, copy=True)
     idx = np.arange(D)
+    if covrec.check_solver(recovery, "recovery") == "device":
+        branch = "1bit" if n_bits == 1 else "fits" if n_bits != np.inf else "plain"
+        cov = _recovered_device(branch, Q, nk, reg, sigma2, quantizer, moments, device, False, True)
+        if n_bits == 1:
+            cq[:, idx, idx] += reg
+        elif n_bits != np.inf:
+            cq = _quantised_covariances(cov, sigma2, quantizer, gains)
+        else:
+            cq = cov + sigma2 * eye
+        return cov, cq
     if n_bits == 1:
         for k in range(K):
             c = np.sin(np.pi / 2 * cq[k].real) + 1j * np.sin(np.pi / 2 * cq[k].imag)
@@ -116,13 +170,7 @@ def quant_covariances(Q, nk, reg, n_bits, sigma2, quantizer, moments, gains):
             c = _eig_clip(c, reg)
             c[idx, idx] += reg
             cov[k] = c
-        A = gains(cov)
-        for k in range(K):
-            Cy = cov[k] + sigma2 * eye
-            dcr = quantized_variance(np.real(np.diag(Cy)), quantizer[0], quantizer[1])
-            c = (A[k][:, None] * Cy) * A[k][None, :].conj()
-            c[idx, idx] = dcr
-            cq[k] = c
+        cq = _quantised_covariances(cov, sigma2, quantizer, gains)
     else:
         for k in range(K):
             c = np.array(cq[k], copy=True)
@@ -136,18 +184,25 @@ def quant_covariances(Q, nk, reg, n_bits, sigma2, quantizer, moments, gains):
     return cov, cq
 
 
-def quant_covariances_inv(Q, nk, reg, n_bits, sigma2, quantizer, moments, gains, F2, Sigma, prev_covs):
+def quant_covariances_inv(Q, nk, reg, n_bits, sigma2, quantizer, moments, gains, F2, Sigma, prev_covs,
+                          recovery="host", device=0):
     """estimate_gaussian_covariances_inv (:880-945): the recovered covariances of the weighted moments Q_k, then the
     inverse-EM (Barton & Fuhrmann) update of Sigma_k with Cinv = pinv(previous covariances) and
-    C_k = F2^H diag(Sigma_k) F2 + reg I.  Sigma (K, P) is updated in place.  Returns (covariances,
-    covariances_quant)."""
+    C_k = F2^H diag(Sigma_k) F2 + reg I.  Sigma (K, P) is updated in place.  recovery "device": the variance fits and
+    the eigenvalue clip run in libqce.so; the Sigma update stays here.  Returns (covariances, covariances_quant)."""
     K, D, _ = Q.shape
     eye = np.eye(D)
     idx = np.arange(D)
     cov = np.empty_like(Q)
     cq = np.array(Q, copy=True)
     Cinv = np.linalg.pinv(np.asarray(prev_covs), hermitian=True)
-    if n_bits == 1:
+    if covrec.check_solver(recovery, "recovery") == "device":
+        if n_bits != 1 and (quantizer is None or quantizer[0] is None):
+            raise AttributeError("'NoneType' object has no attribute 'shape'")
+        cov = _recovered_device("1bit" if n_bits == 1 else "fits", Q, nk, reg, sigma2, quantizer, moments, device,
+                                True, False)  # x0 = 1 here (no x0_vec), no + reg after the clip
+        cq[:, idx, idx] += reg
+    elif n_bits == 1:
         for k in range(K):
             c = np.sin(np.pi / 2 * cq[k].real) + 1j * np.sin(np.pi / 2 * cq[k].imag)
             c[idx, idx] += reg
@@ -265,12 +320,13 @@ def estimate_parameters(obj, be, resp=None, inv=False):
     nk, means, Q = be.mstep(resp)
     centred = None if obj.params.get("zero_mean", False) else means
     moments = lambda: be.moments(resp, centred)  # noqa: E731
+    where = dict(recovery=getattr(obj, "recovery", "host"), device=obj.device)  # objects pickled before the option
     if inv:
         cov, cq = quant_covariances_inv(Q, nk, obj.gm.reg_covar, obj.n_bits, obj.sigma2, obj.quantizer, moments,
-                                        be.gains, obj.F2, obj.gm.Sigma, obj.gm.covariances_)
+                                        be.gains, obj.F2, obj.gm.Sigma, obj.gm.covariances_, **where)
     else:
         cov, cq = quant_covariances(Q, nk, obj.gm.reg_covar, obj.n_bits, obj.sigma2, obj.quantizer, moments,
-                                    be.gains)
+                                    be.gains, **where)
     obj.covariances_quant = cq
     return nk, means, cov
 

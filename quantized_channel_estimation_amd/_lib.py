@@ -24,6 +24,7 @@ OPT_INT8_SLICES = 4
 OPT_FOURIER_PILOTS = 5
 QUANT_UNIFORM, QUANT_LLOYD, QUANT_OTHER = 0, 1, 2
 IO_HOST, IO_DEVICE = 0, 1
+CLIP_PLAIN, CLIP_SIN, CLIP_SIN_SCALED = 0, 1, 2
 OUT_Y, OUT_FEATURES_RAW, OUT_FEATURES_DFT = 0, 1, 2
 COMM_ID_BYTES = 128
 COMM_RCCL, COMM_HOST = 0, 1
@@ -105,6 +106,11 @@ SIGNATURES = {
                                     ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qce_quant_moments": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int,
                                          _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "qce_quant_variance_fit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                              _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "qce_herm_eig_clip": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _vp,
+                                         ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int,
+                                         _vp]),
     "qce_kmeans_lloyd": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                         ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qce_kmeans_seed": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64, _vp,

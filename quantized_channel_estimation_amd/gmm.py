@@ -19,6 +19,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from .covrec import check_solver
 from .kmeans import check_kmeans_option
 
 try:  # the reference keeps its hyper-parameters and fitted weights in an sklearn object (:86-87)
@@ -193,6 +194,8 @@ class Gmm_nbit:
         for name in ("means_cplx", "covs_cplx", "fft_covs", "fft_means", "chol", "F2"):
             setattr(obj, name, copy.deepcopy(getattr(ref, name, None)))
         obj.params = copy.deepcopy(getattr(ref, "params", {}))
+        if hasattr(ref, "recovery"):  # a Gmm_quant's option of later fits
+            obj.recovery = check_solver(ref.recovery, "recovery")
         return obj
 
     @classmethod
@@ -482,9 +485,13 @@ class Gmm_quant(Gmm_nbit):
     branch (:300-327): inf goes through the uniform-quantiser gain, which is the identity, so the
     result is the same; with a Lloyd quantiser the reference overflows, which is mirrored."""
 
-    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, kmeans="host", **gmm_kwargs):
+    def __init__(self, *gmm_args, device=0, precision="f64", fourier_pilots=False, kmeans="host", recovery="host",
+                 **gmm_kwargs):
         super().__init__(*gmm_args, device=device, precision=precision, fourier_pilots=fourier_pilots, kmeans=kmeans,
                          **gmm_kwargs)
+        # covariance recovery of fit's M-step: "host" = the NumPy algebra as in the reference (the default), "device" =
+        # the scalar variance fits and the eigenvalue clips in libqce.so (covrec.variance_fits / eig_clip; opt-in)
+        self.recovery = check_solver(recovery, "recovery")
         self.quantizer = None
         self.sigma2 = None
         self.n_bits = None
@@ -496,7 +503,8 @@ class Gmm_quant(Gmm_nbit):
     def fit(self, h, n_bits, sigma2, quantizer, quant_type, blocks=None, zero_mean=False, _backend=None):
         """EM on quantised observations with covariance recovery (gmm_cplx_quant.py:103-189): 'full' (:155-159) and
         the inverse-EM 'toeplitz' / 'block-toeplitz' (:160-181, with the partial DFT F2), zero mean or with means;
-        device E-step on covariances_quant and device moments, the recovery algebra on the host (_em_quant.py).
+        device E-step on covariances_quant and device moments, the recovery algebra on the host (_em_quant.py) or,
+        with recovery="device", its variance fits and eigenvalue clips on the device.
         The covariance types the reference cannot fit end in the reference's own exception
         (_em_quant.reference_fit_error)."""
         from . import _em_quant
