@@ -449,6 +449,48 @@ int qce_vae_elbo(const float* enc, const float* dec, const float* target, int64_
                  int mode, double n_bits, const int32_t* index, const double* snr_db, double* rows_out,
                  float* grad_enc, float* grad_dec, int device, void* stream);
 
+/* The fused training step (csrc/qce_vae_step.hip): a trainer owns the weights, Adam's two moments and its step count
+ * on the device, and runs one training step of the reference's loop (estimators/vae.py:108-123) as two kernels:
+ * k_vae_step (gather the batch by index, pilot convolutions, encoder, z = mu + exp(s) eps, decoder, the row ELBO of
+ * qce_vae_elbo, the backward pass, one partial gradient per tile of 16 rows) and k_vae_update (sum of the partials in
+ * tile order, loss = -mean_b l_b in FP64, skip rule, torch's default Adam).  Equal state and inputs give bit-identical
+ * results.
+ *
+ * qce_vae_trainer_create: mode 0 'genie' (x is (n_x, 2N), the convolutions are not applied), 1 'noisy', 2 'real';
+ * widths as qce_vae_net_create; weights (n_weights,) float32 in state-dict order, host memory (QCE_IO_HOST) or
+ * device memory (QCE_IO_DEVICE); max_batch bounds B of later calls.  Refused with QCE_ENOTIMPL before any device call:
+ * N outside {16, 32, 64, 128}, P > 4, L > 128, and a network whose LDS need (the stored activations of 16 rows, two
+ * delta buffers and staging; the message states it) exceeds 160 KiB.
+ * qce_vae_trainer_step: one step; all pointers device memory, asynchronous on `stream`, no status read.  x (n_x, P, 2N)
+ * float32 features, target (n_target, 2N) float32, snr_db (n_target,) float64 ('real' only), index (B,) int32 rows of x
+ * and target (clamped; NULL: row b), n_bits as qce_vae_elbo ('real' only), eps (B, L) float32 or NULL: drawn as
+ * qce_vae_sample draws it from (seed, row_offset).  The loss goes to slot step_slot (< QCE_VAE_TRAINER_SLOTS) of the
+ * trainer's loss record together with a flag: 1 when the loss was NaN or above 1000, and then weights, moments and
+ * step count are left untouched.
+ * qce_vae_trainer_grads: the same forward, loss and backward without an update: grads_out (n_weights,) float32,
+ * rows_out (B,) float64 row ELBOs, loss_out one float64; device memory, asynchronous.
+ * qce_vae_trainer_read: the first n slots of the loss record into host arrays; synchronises `stream`.
+ * qce_vae_trainer_get_state / _set_state: weights, exp_avg, exp_avg_sq (device memory, each may be NULL) and the step
+ * count (host); both synchronise `stream`. */
+#define QCE_VAE_TRAINER_SLOTS 4096
+typedef struct qce_vae_trainer qce_vae_trainer;
+int qce_vae_trainer_create(int N, int P, int L, int n_layers, int n_pilot_convs, int mode, const int32_t* widths,
+                           const float* weights, int64_t n_weights, double lr, int64_t max_batch, int io, int device,
+                           qce_vae_trainer** out);
+int qce_vae_trainer_step(qce_vae_trainer* tr, const float* x, int64_t n_x, const float* target, int64_t n_target,
+                         const double* snr_db, const int32_t* index, int64_t B, double n_bits, const float* eps,
+                         uint64_t seed, uint64_t row_offset, int step_slot, void* stream);
+int qce_vae_trainer_grads(qce_vae_trainer* tr, const float* x, int64_t n_x, const float* target, int64_t n_target,
+                          const double* snr_db, const int32_t* index, int64_t B, double n_bits, const float* eps,
+                          uint64_t seed, uint64_t row_offset, float* grads_out, double* rows_out, double* loss_out,
+                          void* stream);
+int qce_vae_trainer_read(qce_vae_trainer* tr, double* losses_out, int32_t* skipped_out, int n, void* stream);
+int qce_vae_trainer_get_state(qce_vae_trainer* tr, float* weights_out, float* exp_avg_out, float* exp_avg_sq_out,
+                              int64_t* step_out, void* stream);
+int qce_vae_trainer_set_state(qce_vae_trainer* tr, const float* weights, const float* exp_avg, const float* exp_avg_sq,
+                              int64_t step, void* stream);
+int qce_vae_trainer_destroy(qce_vae_trainer* tr);
+
 /* Page-locked host memory (hipHostMalloc / hipHostFree).  QCE_IO_HOST calls DMA straight from / into page-locked
  * arrays (and from / into pageable ones they can register for the call): a caller that allocates its result arrays
  * here, and reuses them, saves the page faults of fresh pageable memory (the Python layer's result pool, _lib.py). */

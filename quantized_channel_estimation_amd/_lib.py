@@ -73,6 +73,17 @@ SIGNATURES = {
     "qce_vae_sample_bwd": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, ctypes.c_int, _vp]),
     "qce_vae_elbo": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "qce_vae_trainer_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, _vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "qce_vae_trainer_step": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64,
+                                            ctypes.c_double, _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _vp]),
+    "qce_vae_trainer_grads": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64,
+                                             ctypes.c_double, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "qce_vae_trainer_read": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp]),
+    "qce_vae_trainer_get_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp]),
+    "qce_vae_trainer_set_state": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp]),
+    "qce_vae_trainer_destroy": (ctypes.c_int, [_vp]),
     "qce_model_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double]),
     "qce_estimate_assigned": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),
     "qce_estimate_ls": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),

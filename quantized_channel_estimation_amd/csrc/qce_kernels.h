@@ -474,6 +474,65 @@ hipError_t qce_launch_vae_sample(const float* enc, const float* eps_in, long lon
 hipError_t qce_launch_vae_sample_bwd(const float* enc, const float* eps, const float* gz, long long B, int L,
                                      float* g_enc, hipStream_t st);
 hipError_t qce_launch_vae_elbo(const QceVaeElboArgs& a, hipStream_t st);
+// The fused VAE training step (qce_vae_step.hip): k_vae_step (gather, forward, row ELBO, backward, per-tile partial
+// gradients) and k_vae_update (tile-ordered reduction, skip rule, Adam).  Parameters are one flat float32 array in
+// state-dict order: per pilot convolution weight (out, in) then bias, then per encoder and decoder layer weight
+// (out, in) row-major then bias.
+#define QCE_VAE_STEP_LDS_LIMIT (160 * 1024)  // LDS bytes of one workgroup (one CU of gfx950)
+#define QCE_VAE_STEP_MAX_CONV_PARAMS (QCE_VAE_NET_MAX_CONVS * (QCE_VAE_MAX_PILOTS * QCE_VAE_MAX_PILOTS + QCE_VAE_MAX_PILOTS))
+#define QCE_VAE_LOSS_SKIP 1000.0             // a step whose loss is NaN or above this updates nothing (vae.py:120-121)
+struct QceVaeStepLayer {
+  int in, out;        // W is (out, in)
+  int w_off, b_off;   // floats into the flat parameters (and into a row of partials)
+  int relu;           // ReLU on the output
+  int src, dst;       // LDS float offsets of the input and the output activations (16 rows each)
+  int s_src, s_dst;   // their row strides: the width rounded up to 16, plus 4
+};
+struct QceVaeStepArgs {
+  long long B, n_x, T;     // batch rows; rows of x; rows of t (and entries of snr)
+  int N, P, L;             // P: channels of a row of x (1 without convolutions)
+  int mode;                // loss: 0 genie / noisy, 1 real
+  int n_bits;              // mode 1: 1..8, 0 = no quantiser
+  double step;             // mode 1: the standard uniform step
+  float sqrt_pi_f;
+  int nconv;
+  int conv_ch[QCE_VAE_NET_MAX_CONVS + 1];
+  int conv_off[QCE_VAE_NET_MAX_CONVS];  // floats into the parameters: weight (out, in), then bias (out)
+  int n_conv_params;
+  int nenc, nlayers;       // layers [0, nenc): encoder (the last gives [mu | s]), the rest: decoder
+  QceVaeStepLayer layer[2 * QCE_VAE_NET_MAX_LAYERS];
+  // LDS float offsets: raw x tile (16 x P x 2N, with convolutions), z's eps (16 x L), the KL gradient (16 x 2L), the two
+  // delta buffers (16 x s_delta each); the convolutions' reduction staging shares the bytes of the delta buffers' tail
+  int x_off, eps_off, kl_off, d0_off, d1_off, s_delta, red_off;
+  unsigned lds_bytes;
+  int n_params;
+  const float* w;          // flat parameters
+  const float* x;          // (n_x, P, 2N) features
+  const float* t;          // (T, 2N) targets
+  const int* index;        // (B,) rows of x / t, clamped; or NULL: row b
+  const double* snr;       // (T,), mode 1
+  const float* eps;        // (B, L), or NULL: drawn from (seed, row_offset)
+  unsigned long long seed, row_offset;
+  double* rows;            // (B,) row ELBOs
+  float* partials;         // (tiles, n_params)
+  const long long* count;  // Adam's step count; the kernel copies it to *count_snap for k_vae_update
+  long long* count_snap;
+};
+struct QceVaeUpdateArgs {
+  long long B;
+  int tiles, n_params;
+  const float* partials;
+  const double* rows;
+  float *w, *m, *v;             // NULL w: no update (gradients only)
+  const long long* count_snap;  // the step count before this step
+  long long* count;
+  double lr;
+  double* loss_out;             // losses[slot], or the caller's scalar
+  int* skipped_out;             // skipped[slot], or NULL
+  float* grads_out;             // (n_params,) reduced gradient, or NULL
+};
+hipError_t qce_launch_vae_step(const QceVaeStepArgs& a, hipStream_t st);
+hipError_t qce_launch_vae_update(const QceVaeUpdateArgs& a, hipStream_t st);
 // Bussgang LS with column-orthogonal A_eff (qce_genie.hip; estimators/LS.py)
 hipError_t qce_launch_ls(long long B, int N, int M, const double2* y, const long long* comp, const double2* Aeff,
                          double2* h, hipStream_t st);

@@ -22,6 +22,7 @@
 //   dloss/dv_m = dl/dc_m exp(-v_m) / B
 //
 // Arithmetic: inputs widened to FP64; exp, log, sums and gradients in FP64; one rounding to float32 at the store.
+// The row math (elbo_row) and the eps draw live in qce_vae_row_dev.h, which k_vae_step (qce_vae_step.hip) includes too.
 //
 // Layout of k_vae_elbo: a row lives in a group of G = min(N, 64) lanes of one wave (four rows per wave at N = 16, two
 // at N = 32, the whole wave from N = 64), lane j holding the E = N / G consecutive elements j E .. j E + E - 1 in
@@ -38,52 +39,14 @@
 // backward reads.
 #include "qce_common.h"
 #include "qce_kernels.h"
-#include "qce_observe_dev.h"
+#include "qce_vae_row_dev.h"
 
 namespace {
 
-using namespace qce_obs;
+using namespace qce_vae_row;  // the row math and the eps draw, shared with k_vae_step
 
 constexpr int VT_THREADS = 256;
 constexpr int VT_MAX_BLOCKS = 4096;  // the element-wise kernels walk the rest grid-stride
-
-template <int G>
-QCE_DEV double group_sum(double v) {
-#pragma unroll
-  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-  return v;
-}
-
-template <int E>
-QCE_DEV void load_vec(const float* p, double (&o)[E]) {
-  if constexpr (E == 4) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    o[0] = f.x, o[1] = f.y, o[2] = f.z, o[3] = f.w;
-  } else if constexpr (E == 2) {
-    const float2 f = *reinterpret_cast<const float2*>(p);
-    o[0] = f.x, o[1] = f.y;
-  } else {
-    o[0] = *p;
-  }
-}
-
-template <int E>
-QCE_DEV void store_vec(float* p, const double (&v)[E]) {
-  if constexpr (E == 4) *reinterpret_cast<float4*>(p) = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-  else if constexpr (E == 2) *reinterpret_cast<float2*>(p) = make_float2((float)v[0], (float)v[1]);
-  else *p = (float)v[0];
-}
-
-// One standard normal for element counter e of stream `seed`.
-QCE_DEV double eps_draw(unsigned long long seed, unsigned long long e) {
-  const uint4 r = philox(make_uint4((uint32_t)e, (uint32_t)(e >> 32), DOMAIN_VAE_EPS, 0u),
-                         make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-  const unsigned long long a = ((unsigned long long)r.x << 32 | r.y) >> 11;  // 53 bits
-  const unsigned long long b = ((unsigned long long)r.z << 32 | r.w) >> 11;
-  const double u1 = (double)(a + 1) * 0x1.0p-53;  // (0, 1]
-  const double u2 = (double)b * 0x1.0p-53;        // [0, 1)
-  return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
-}
 
 __global__ __launch_bounds__(VT_THREADS) void k_vae_sample(const float* __restrict__ enc, const float* __restrict__ eps_in,
                                                            long long B, int L, unsigned long long seed,
@@ -129,90 +92,11 @@ __global__ __launch_bounds__(VT_THREADS) void k_vae_elbo(QceVaeElboArgs a) {
     tb = ix < 0 ? 0 : (ix >= a.T ? a.T - 1 : ix);
   }
   const int L = a.L;
-  const double Bd = (double)a.B;
-
-  // latent part
-  const float* er = a.enc + b * 2 * L;
-  float* ge = a.g_enc + b * 2 * L;
-  double acc = 0.0;
-  for (int l = j; l < L; l += G) {
-    const double mu = er[l], s = er[L + l];
-    const double e2 = exp(2.0 * s);
-    acc += s - 0.5 * mu * mu - 0.5 * e2;
-    if (live) {
-      ge[l] = (float)(mu / Bd);
-      ge[L + l] = (float)(-(1.0 - e2) / Bd);
-    }
-  }
-
-  // decoder part
-  double v[E], tr[E], ti[E], gv[E];
-  load_vec<E>(a.dec + b * N + j * E, v);
-  load_vec<E>(a.t + tb * 2 * N + j * E, tr);
-  load_vec<E>(a.t + tb * 2 * N + N + j * E, ti);
-  if (MODE == 0) {
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-      const double an = tr[k] * tr[k] + ti[k] * ti[k];
-      const double ea = exp(v[k]) * an;
-      acc += v[k] - ea;
-      gv[k] = -(1.0 - ea) / Bd;
-    }
-  } else {
-    const double s2 = pow(10.0, -a.snr[tb] / 10.0);
-    double c[E], ev[E], csum = 0.0;
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-      ev[k] = exp(-v[k]);
-      c[k] = ev[k] + s2;
-      csum += c[k];
-    }
-    const double cbar = group_sum<G>(csum) / (double)N;
-    double beta = 1.0, dbeta = 0.0;
-    if (a.n_bits > 0) {
-      const double delta = sqrt((1.0 + s2) / 2.0) * a.step;
-      const double k2 = (double)((float)delta / a.sqrt_pi_f);
-      const int nterm = (1 << a.n_bits) - 1, half = 1 << (a.n_bits - 1);
-      const double d2 = delta * delta;
-      double S = 0.0, S2 = 0.0;
-      for (int i = 1 + j; i <= nterm; i += G) {
-        const double m = (double)(i - half);
-        const double w = d2 * m * m / cbar;
-        const double e = exp(-w);
-        S += e;
-        S2 += e * w / cbar;
-      }
-      S = group_sum<G>(S);
-      S2 = group_sum<G>(S2);
-      const double rs = k2 / sqrt(cbar);
-      const double g = rs * S;
-      const double dg = -g / (2.0 * cbar) + rs * S2;
-      const double g2 = g * g;
-      beta = g2 > 1.0 ? 1.0 : g2;
-      dbeta = g2 <= 1.0 ? 2.0 * g * dg : 0.0;
-    }
-    double q[E], sq = 0.0, sqc = 0.0;
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-      const double an = tr[k] * tr[k] + ti[k] * ti[k];
-      const double cp = a.n_bits > 0 ? beta * c[k] + (1.0 - beta) * cbar : c[k];
-      const double ic = 1.0 / cp;
-      acc += -log(cp) - an * ic;
-      q[k] = -ic + an * ic * ic;
-      sq += q[k];
-      sqc += q[k] * (c[k] - cbar);
-    }
-    sq = group_sum<G>(sq);
-    sqc = group_sum<G>(sqc);
-    const double common = ((1.0 - beta) * sq + dbeta * sqc) / (double)N;
-#pragma unroll
-    for (int k = 0; k < E; ++k) gv[k] = (beta * q[k] + common) * ev[k] / Bd;
-  }
-  acc = group_sum<G>(acc);
-  if (live) {
-    store_vec<E>(a.g_dec + b * N + j * E, gv);
-    if (j == 0) a.rows[b] = acc;
-  }
+  const RealConst rc{a.n_bits, a.step, a.sqrt_pi_f};
+  const float* t = a.t + tb * 2 * N;
+  const double acc = elbo_row<G, E, MODE>(j, live, L, (double)a.B, a.enc + b * 2 * L, a.g_enc + b * 2 * L, a.dec + b * N, t,
+                                          t + N, MODE == 1 ? a.snr + tb : nullptr, rc, a.g_dec + b * N);
+  if (live && j == 0) a.rows[b] = acc;
 }
 
 unsigned ew_grid(long long n) {

@@ -20,7 +20,10 @@ weights start from other draws of the same distributions (nn.Linear's / nn.Conv1
 noise.  Checkpoints carry the reference's keys and state-dict names.  In 'real' mode both the training and the
 validation observations are DFT features whatever ``fft_pre`` says; the reference transforms its training set always
 and its validation set only with ``fft_pre`` (:64-65, :100), so with ``fft_pre=False`` its validation loss is of another
-kind than its training loss, and than the validation loss here.
+kind than its training loss, and than the validation loss here.  ``train(..., fused=True)`` runs the same loop with
+every training step inside libqce.so (csrc/qce_vae_step.hip, ``qce_vae_trainer_*``): gather, layers, loss, backward and
+Adam in two kernels on weights and optimiser state the library holds, one host read per epoch; ``step_gradients``
+returns that step's loss and parameter gradients without an update.  The default stays the torch path.
 
 The reference's behaviour is kept where it is observable, including its failures:
 
@@ -278,6 +281,39 @@ def elbo_loss(enc_out, dec_out, target, *, mode, n_bits=1, snr_db=None, index=No
     return (loss, rows) if return_rows else loss
 
 
+def _widths(params):
+    """The channel counts of the pilot convolutions (P .. 1), the encoder's widths (2N .. 2L) and the decoder's (L .. N)
+    in one int32 array, as ``qce_vae_net_create`` and ``qce_vae_trainer_create`` take them."""
+    N, P, L, nl = (int(params[k]) for k in ("n_antennas", "n_pilots", "latent_dim", "n_layers"))
+    npc = int(params.get("n_pilot_convs", 0))
+    return np.concatenate([np.linspace(P, 1, npc + 1, dtype=int), np.linspace(2 * N, 2 * L, nl + 1, dtype=int),
+                           np.linspace(L, N, nl + 1, dtype=int)]).astype(np.int32)
+
+
+def fused_step_lds_bytes(params):
+    """LDS bytes one workgroup of the fused training step (``k_vae_step``) needs for these params, as
+    ``qce_vae_trainer_create`` computes them: the stored activations of 16 rows (one buffer per layer input and output,
+    row stride = width rounded up to 16, plus 4 floats), the raw tile of the pilot convolutions, eps and the KL
+    gradient, two delta buffers of the widest layer, and the gather table."""
+    N, P, L, nl = (int(params[k]) for k in ("n_antennas", "n_pilots", "latent_dim", "n_layers"))
+    npc = 0 if params["vae_mode"] == "genie" else int(params.get("n_pilot_convs", 0))
+    conv = np.linspace(P, 1, npc + 1, dtype=int)
+    widths = [2 * N] + [int(v) for v in np.linspace(2 * N, 2 * L, nl + 1, dtype=int)[1:]]
+    widths += [int(v) for v in np.linspace(L, N, nl + 1, dtype=int)]
+    up16 = lambda v: (v + 15) // 16 * 16  # noqa: E731
+    floats = sum(16 * (up16(v) + 4) for v in widths)
+    floats = max(floats, 256 * sum(int(conv[i + 1] * conv[i] + conv[i + 1]) for i in range(npc)))
+    if npc:
+        floats += 16 * P * 2 * N
+    floats += 16 * L + 16 * 2 * L + 2 * 16 * (up16(max(widths)) + 4)
+    return 4 * floats + 256
+
+
+FUSED_STEP_LDS_LIMIT = 160 * 1024  # bytes of LDS per workgroup
+FUSED_STEP_SLOTS = 4096            # entries of the trainer's loss record (QCE_VAE_TRAINER_SLOTS)
+_MODE_CODE = {"genie": 0, "noisy": 1, "real": 2}
+
+
 def layer_shapes(params):
     """{state-dict name: shape} of the reference's DNN_VAE (:237-267) for these params."""
     N, P, L, nl = (int(params[k]) for k in ("n_antennas", "n_pilots", "latent_dim", "n_layers"))
@@ -313,10 +349,12 @@ class VAE_nbit:
             raise NotImplementedError("several pilots need n_pilot_convs >= 1 (the reference's encoder takes one row)")
         self._w = None
         self._net = None  # the packed handle of the fused forward (qce_vae_net), built on first use
+        self._trainer = None  # (handle, max_batch) of the fused training step (qce_vae_trainer), built on first use
 
     def __del__(self):
         try:
             self._drop_net()
+            self._drop_trainer()
         except Exception:  # interpreter teardown
             pass
 
@@ -338,8 +376,7 @@ class VAE_nbit:
         p = self.params
         N, P, L, nl = (int(p[k]) for k in ("n_antennas", "n_pilots", "latent_dim", "n_layers"))
         npc = int(p.get("n_pilot_convs", 0))
-        widths = np.concatenate([np.linspace(P, 1, npc + 1, dtype=int), np.linspace(2 * N, 2 * L, nl + 1, dtype=int),
-                                 np.linspace(L, N, nl + 1, dtype=int)]).astype(np.int32)
+        widths = _widths(p)
         flat = torch.cat([self._w[name].detach().reshape(-1) for name in layer_shapes(p)]).contiguous()
         out = ctypes.c_void_p()
         _lib.check(_lib.load().qce_vae_net_create(N, P, L, nl, npc, int(p["vae_mode"] == "genie"), _lib.ptr(widths),
@@ -350,8 +387,153 @@ class VAE_nbit:
         return out
 
     def close(self):
-        """Free the library's handle of the fused forward (it is rebuilt on the next fused call)."""
+        """Free the library's handles (fused forward, fused training step); they are rebuilt on the next fused call."""
         self._drop_net()
+        self._drop_trainer()
+
+    def _drop_trainer(self):
+        tr, self._trainer = getattr(self, "_trainer", None), None
+        if tr is not None:
+            _lib.load().qce_vae_trainer_destroy(tr[0])
+
+    def _trainer_handle(self, max_batch):
+        """The library's trainer for the current weights (``qce_vae_trainer_create``: it copies them and starts Adam
+        from zero moments), cached until the weights are replaced or a larger batch comes."""
+        if self._w is None:
+            raise RuntimeError("no weights: call load_state_dict, from_checkpoint or train first")
+        if self._trainer is not None and self._trainer[1] >= max_batch:
+            return self._trainer[0]
+        self._drop_trainer()
+        import ctypes
+        import torch
+        p = self.params
+        N, P, L, nl = (int(p[k]) for k in ("n_antennas", "n_pilots", "latent_dim", "n_layers"))
+        flat = torch.cat([self._w[name].detach().reshape(-1) for name in layer_shapes(p)]).contiguous()
+        out = ctypes.c_void_p()
+        _lib.check(_lib.load().qce_vae_trainer_create(N, P, L, nl, int(p.get("n_pilot_convs", 0)), _MODE_CODE[p["vae_mode"]],
+                                                      _lib.ptr(_widths(p)), _lib.ptr(flat), flat.numel(),
+                                                      float(p.get("lr", 1e-3)), int(max_batch), _lib.IO_DEVICE,
+                                                      flat.device.index or 0, ctypes.byref(out)))
+        self._trainer = (out, int(max_batch))
+        _lib._live["vae_net"].add(self)  # closed at exit while the HIP runtime is still up
+        return out
+
+    def _step_inputs(self, x, target, snr_db, index, eps):
+        """The checked device arguments of one fused step: (x, n_x, target, n_target, snr, index, B, n_bits, eps)."""
+        import torch
+        p = self.params
+        N, L, mode = int(p["n_antennas"]), int(p["latent_dim"]), p["vae_mode"]
+        pin = int(p["n_pilots"]) if (mode != "genie" and int(p.get("n_pilot_convs", 0))) else 1
+        if not _is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2:
+            raise TypeError("x must be a float32 CUDA tensor (n, P, 2N) or (n, 2N)")
+        n_x = x.shape[0]
+        x = x.contiguous()
+        if x.numel() != n_x * pin * 2 * N:
+            raise ValueError(f"x must be ({n_x}, {pin}, {2 * N}), got {tuple(x.shape)}")
+        tgt = _f32_device(target.detach() if _is_tensor(target) else target, "target", 2 * N)
+        B = n_x
+        if index is not None:
+            if not _is_tensor(index) or not index.is_cuda or index.dim() != 1:
+                raise ValueError("index must be a CUDA tensor (B,)")
+            B = index.shape[0]
+            index = index.to(torch.int32).contiguous()
+        elif tgt.shape[0] < B:
+            raise ValueError(f"target has {tgt.shape[0]} rows for a batch of {B}")
+        if B < 1 or n_x < 1 or tgt.shape[0] < 1:
+            raise ValueError("empty batch")
+        nb = 1.0
+        if mode == "real":
+            nb = _nbits(p["n_bits"])
+            if snr_db is None:
+                raise ValueError("mode 'real' needs snr_db, one value per target row")
+            snr_db = torch.as_tensor(snr_db, device=x.device).to(torch.float64).reshape(-1).contiguous()
+            if snr_db.shape[0] != tgt.shape[0]:
+                raise ValueError(f"snr_db must have {tgt.shape[0]} entries, got {snr_db.shape[0]}")
+        else:
+            snr_db = None
+        if eps is not None:
+            eps = _f32_device(eps, "eps", L)
+            if eps.shape[0] != B:
+                raise ValueError(f"eps must be ({B}, {L}), got {tuple(eps.shape)}")
+        return x, n_x, tgt, tgt.shape[0], snr_db, index, B, float(nb), eps
+
+    def step_gradients(self, x, target, *, eps=None, seed=0, row_offset=0, snr_db=None, index=None):
+        """(loss, rows, {name: grad}) of one training batch from the fused step kernel (``qce_vae_trainer_grads``:
+        forward, ELBO, backward and the reduction over the batch in libqce.so, no update): the loss -mean_b l_b
+        (float), the row ELBOs (B,) float64 and the gradient of the loss for every parameter, float32 tensors under the
+        state-dict names.  x (n, P, 2N) (or (n, 2N)) and target (T, 2N) are float32 CUDA tensors; row b uses row
+        ``index[b]`` of both (and of ``snr_db`` (T,), 'real' mode), or row b.  ``eps`` (B, L), or None: drawn as
+        ``reparameterize`` draws it from ``seed`` / ``row_offset``.  For tests and for an optimiser of the caller's."""
+        import torch
+        self._check_fused()
+        x, n_x, tgt, T, snr, index, B, nb, eps = self._step_inputs(x, target, snr_db, index, eps)
+        tr = self._trainer_handle(B)
+        dev, st = _dev_stream(x)
+        shapes = layer_shapes(self.params)
+        grads = torch.empty(sum(int(np.prod(s)) for s in shapes.values()), dtype=torch.float32, device=x.device)
+        rows = torch.empty(B, dtype=torch.float64, device=x.device)
+        loss = torch.empty(1, dtype=torch.float64, device=x.device)
+        _lib.check(_lib.load().qce_vae_trainer_grads(tr, _lib.ptr(x), n_x, _lib.ptr(tgt), T, _lib.ptr(snr), _lib.ptr(index),
+                                                     B, nb, _lib.ptr(eps), int(seed), int(row_offset), _lib.ptr(grads),
+                                                     _lib.ptr(rows), _lib.ptr(loss), st))
+        out, off = {}, 0
+        for name, shape in shapes.items():
+            n = int(np.prod(shape))
+            out[name] = grads[off:off + n].view(shape)
+            off += n
+        return float(loss.item()), rows, out
+
+    def _fused_step(self, x, target, *, eps=None, seed=0, row_offset=0, snr_db=None, index=None, slot=0, max_batch=None):
+        """One fused training step (``qce_vae_trainer_step``) on the trainer's state; asynchronous.  The loss and the
+        skip flag go to entry ``slot`` of the trainer's record (``_fused_read``)."""
+        x, n_x, tgt, T, snr, index, B, nb, eps = self._step_inputs(x, target, snr_db, index, eps)
+        tr = self._trainer_handle(max(B, max_batch or 0))
+        _lib.check(_lib.load().qce_vae_trainer_step(tr, _lib.ptr(x), n_x, _lib.ptr(tgt), T, _lib.ptr(snr), _lib.ptr(index),
+                                                    B, nb, _lib.ptr(eps), int(seed), int(row_offset), int(slot),
+                                                    _dev_stream(x)[1]))
+        return x, tgt, snr, index, eps  # what the step reads: the caller keeps them until it has synchronised
+
+    def _fused_read(self, n):
+        """(losses (n,) float64, skipped (n,) bool) of the trainer's record: one synchronising copy."""
+        import torch
+        losses, skipped = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.int32)
+        dev = self._device()
+        _lib.check(_lib.load().qce_vae_trainer_read(self._trainer[0], _lib.ptr(losses), _lib.ptr(skipped), n,
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+        return losses, skipped.astype(bool)
+
+    def _fused_state(self):
+        """({name: weight}, {name: exp_avg}, {name: exp_avg_sq}, step count) of the trainer, as fresh tensors."""
+        import ctypes
+        import torch
+        dev = self._device()
+        shapes = layer_shapes(self.params)
+        n = sum(int(np.prod(s)) for s in shapes.values())
+        flat = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3)]
+        step = ctypes.c_int64()
+        _lib.check(_lib.load().qce_vae_trainer_get_state(self._trainer[0], _lib.ptr(flat[0]), _lib.ptr(flat[1]),
+                                                         _lib.ptr(flat[2]), ctypes.byref(step),
+                                                         torch.cuda.current_stream(dev).cuda_stream))
+        out = []
+        for f in flat:
+            d, off = {}, 0
+            for name, shape in shapes.items():
+                k = int(np.prod(shape))
+                d[name] = f[off:off + k].view(shape)
+                off += k
+            out.append(d)
+        return out[0], out[1], out[2], int(step.value)
+
+    def _fused_set_state(self, weights=None, exp_avg=None, exp_avg_sq=None, step=0):
+        """Replace the trainer's weights / moments ({name: tensor}, or None: kept) and its step count."""
+        import torch
+        dev = self._device()
+        flat = [None if d is None else torch.cat([d[name].detach().to(device=dev, dtype=torch.float32).reshape(-1)
+                                                  for name in layer_shapes(self.params)]).contiguous()
+                for d in (weights, exp_avg, exp_avg_sq)]
+        _lib.check(_lib.load().qce_vae_trainer_set_state(self._trainer[0], _lib.ptr(flat[0]), _lib.ptr(flat[1]),
+                                                         _lib.ptr(flat[2]), int(step),
+                                                         torch.cuda.current_stream(dev).cuda_stream))
     def _device(self):
         import torch
         d = self.params.get("device", 0)
@@ -377,6 +559,7 @@ class VAE_nbit:
                 raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
             w[name] = t
         self._drop_net()
+        self._drop_trainer()
         self._w = w
         return self
 
@@ -468,7 +651,26 @@ class VAE_nbit:
         s = np.linspace(1, p["snr_scale_fac"], len(p["snrs"]))  # :18-20
         return s / np.sum(s)
 
-    def _check_trainable(self, h_test):
+    def _check_fused(self):
+        """The refusals of the fused training step alone (``qce_vae_trainer_create`` repeats them)."""
+        p = self.params
+        if not p.get("zeromean", True):
+            raise ValueError(ZEROMEAN_MESSAGE)
+        N, P, L = int(p["n_antennas"]), int(p["n_pilots"]), int(p["latent_dim"])
+        pilot_vector(None, N)
+        if N == 256:
+            raise NotImplementedError("n_antennas = 256 is not covered by the fused training step: the activations of 16 "
+                                      "rows do not fit the LDS of one workgroup (train with fused=False)")
+        if P > MAX_PILOTS:
+            raise NotImplementedError(f"at most {MAX_PILOTS} pilots, got {P}")
+        if L < 1 or L > MAX_LATENT:
+            raise NotImplementedError(f"latent_dim must lie in [1, {MAX_LATENT}], got {L}")
+        need = fused_step_lds_bytes(p)
+        if need > FUSED_STEP_LDS_LIMIT:
+            raise NotImplementedError(f"the fused training step needs {need} bytes of LDS per workgroup for this network, "
+                                      f"it covers up to {FUSED_STEP_LDS_LIMIT} (train with fused=False)")
+
+    def _check_trainable(self, h_test, fused=False):
         """The refusals of ``train``, before anything is uploaded."""
         p = self.params
         if not p.get("zeromean", True):
@@ -486,6 +688,8 @@ class VAE_nbit:
             if P > 1:
                 raise NotImplementedError("vae_mode 'real' trains with one pilot: the reference transforms the whole "
                                           "row of length P N and its encoder takes 2 N inputs")
+        if fused:
+            self._check_fused()
         if h_test is None:
             raise UnboundLocalError(HTEST_MESSAGE)  # the reference's first validation pass (:132)
 
@@ -501,6 +705,7 @@ class VAE_nbit:
             t = (torch.rand(shape, generator=gen, device=dev, dtype=torch.float32) * 2 - 1) * bound
             w[name] = t.requires_grad_(True)
         self._drop_net()
+        self._drop_trainer()
         self._w = w
 
     def _train_data(self, h_dev, snr_list, seed, row_offset):
@@ -518,14 +723,19 @@ class VAE_nbit:
             return x, x.reshape(-1, 2 * N), snrs
         return x, None, None
 
-    def train(self, h_train, h_test, snr_list, *, seed=0, file_vae=None):
+    def train(self, h_train, h_test, snr_list, *, seed=0, file_vae=None, fused=False):
         """The reference's training loop (:15-154) on the device; returns (losses_all, losses_all_test), the clipped
         epoch means of the training and validation loss.  ``params`` additionally needs lr, batch_size, epochs,
         snr_scale (and snr_scale_fac, snrs), and for the default checkpoint name sim_id, model_type, n_paths, n_train.
         The trained weights stay in the object (``forward_nosamp`` / ``estimate_from_y`` work at once) and are saved
         after every epoch to ``file_vae`` (default: the reference's name pattern), a file ``from_checkpoint`` reads.
-        ``seed`` keys every draw: initial weights, batches, observations and eps."""
-        self._check_trainable(h_test)
+        ``seed`` keys every draw: initial weights, batches, observations and eps.
+
+        ``fused``: every training step runs as two kernels of libqce.so (``k_vae_step``: gather, forward, ELBO and
+        backward; ``k_vae_update``: reduction, skip rule, Adam; csrc/qce_vae_step.hip) on weights and Adam state the
+        library holds, and the host reads the losses once per epoch.  Same initial weights, batches, observations and
+        eps as the default loop; N = 256 and networks beyond 160 KiB of LDS per workgroup are refused."""
+        self._check_trainable(h_test, fused)
         import torch
         p = self.params
         mode, N, bs = p["vae_mode"], int(p["n_antennas"]), int(p["batch_size"])
@@ -537,6 +747,8 @@ class VAE_nbit:
         gen.manual_seed(int(seed))
         self._init_weights(gen)
         opti = torch.optim.Adam(list(self._w.values()), lr=p["lr"])
+        if fused:
+            self._trainer_handle(bs)  # takes a copy of the initial weights; the optimiser above only shapes the checkpoint
         if file_vae is None:
             file_vae = (f'results/vae/saves/VAE{p["vae_mode"]}_{p["sim_id"]}_{p["model_type"]}_paths={p["n_paths"]}_ant='
                         f'{p["n_antennas"]}_ntrain={p["n_train"]}.pt')  # :76-78
@@ -568,7 +780,9 @@ class VAE_nbit:
                 x_tr, tt, snr_tr = self._train_data(h_tr, snr_list, seed, epoch * n_train)
                 t_train = tt if tt is not None else t_train
             loss_epoch = []
-            for _ in range(n_train // bs):
+            if fused:
+                loss_epoch = self._fused_epoch(x_tr, t_train, snr_tr, n_train, bs, gen, seed, drawn)
+            for _ in range(0 if fused else n_train // bs):
                 opti.zero_grad()
                 loss = loss_of(x_tr, t_train, snr_tr, n_train)
                 val = float(loss.detach())  # the skip rule's host read (:120)
@@ -580,6 +794,7 @@ class VAE_nbit:
             if not loss_epoch or np.isnan(np.mean(loss_epoch)):
                 continue
             losses_all.append(np.clip(np.mean(loss_epoch), -np.inf, LOSS_SKIP))
+            optim_state = self._fused_pull(opti) if fused else opti.state_dict()
             with torch.no_grad():
                 loss_test = [loss_of(x_te, t_test, snr_te, n_test) for _ in range(n_test // bs)]
                 loss_test = torch.stack(loss_test).cpu().numpy().astype(np.float64) if loss_test else np.full(1, np.nan)
@@ -587,12 +802,48 @@ class VAE_nbit:
             parent = os.path.dirname(file_vae)
             if parent:
                 os.makedirs(parent, exist_ok=True)
-            torch.save({"model": {k: v.detach() for k, v in self._w.items()}, "optim": opti.state_dict(),
+            torch.save({"model": {k: v.detach() for k, v in self._w.items()}, "optim": optim_state,
                         "loss_all": losses_all, "epoch": epoch, "params": p}, file_vae)
         for v in self._w.values():
             v.requires_grad_(False)
         self._drop_net()  # the optimiser has updated the weights in place
+        self._drop_trainer()
         return losses_all, losses_all_test
+
+    def _fused_epoch(self, x_all, t_all, snr_all, n_rows, bs, gen, seed, drawn):
+        """The training steps of one epoch on the fused step (two kernels each, no host read); returns the losses of
+        the steps that were not skipped, from one read of the trainer's record per FUSED_STEP_SLOTS steps.  The
+        batches and the eps counters are those of the unfused loop."""
+        import torch
+        dev = x_all.device
+        if snr_all is not None:
+            snr_all = torch.as_tensor(snr_all, device=dev).to(torch.float64).reshape(-1).contiguous()
+        steps, kept = n_rows // bs, []
+        for s0 in range(0, steps, FUSED_STEP_SLOTS):
+            n = min(FUSED_STEP_SLOTS, steps - s0)
+            alive = []  # the steps' inputs, until the read below has synchronised
+            for s in range(n):
+                idx = torch.randperm(n_rows, generator=gen, device=dev)[:bs].to(torch.int32)
+                alive.append(self._fused_step(x_all, t_all, snr_db=snr_all, index=idx, seed=seed, row_offset=drawn[0],
+                                              slot=s, max_batch=bs))
+                drawn[0] += bs
+            losses, skipped = self._fused_read(n)
+            kept += [float(np.float32(v)) for v, sk in zip(losses, skipped) if not sk]
+        return kept
+
+    def _fused_pull(self, opti):
+        """Copy the trainer's weights into ``_w`` (in place) and return its Adam state as a state dict of ``opti``."""
+        import torch
+        w, m, v, step = self._fused_state()
+        with torch.no_grad():
+            for name, t in self._w.items():
+                t.copy_(w[name])
+        self._drop_net()
+        sd = opti.state_dict()
+        if step > 0:
+            sd["state"] = {i: {"step": torch.tensor(float(step)), "exp_avg": m[name], "exp_avg_sq": v[name]}
+                           for i, name in enumerate(self._w)}
+        return sd
 
     def _estimate(self, y, snr, h):
         import torch

@@ -3,9 +3,13 @@ same step with the loss and the reparameterisation composed of torch operations 
 this package had before: ``composed_loss`` below, the formulas of DESIGN.md's "VAE training" section in float32 with
 ordinary broadcasting (the gain sum is one broadcast exp over the quantiser's levels).
 
-Settings: N = 64, L = 16, n_layers = 4, batch 200, P = 1; 'noisy' 1 bit and 'real' 3 bit.  Both variants share the
-layers (torch.nn.functional, float32), the weights' initial values, Adam, the batch draw and the index_select of the
-encoder input; they differ in what lies between and around the layers.
+A third variant, ``step``, is the fused training step of ``VAE_nbit.train(fused=True)`` (csrc/qce_vae_step.hip): the
+batch draw stays torch's, everything else is two kernels of libqce.so on weights and Adam state the library holds, and
+the host reads the losses once per window (the loop's once per epoch) instead of once per step.
+
+Settings: N = 64, L = 16, n_layers = 4, batch 200, P = 1; 'noisy' 1 bit and 'real' 3 bit.  The first two variants share
+the layers (torch.nn.functional, float32), the weights' initial values, Adam, the batch draw and the index_select of
+the encoder input; they differ in what lies between and around the layers.
 
 Timing: after a warm-up, windows of at least 0.5 s; the two variants alternate and the median of 5 windows each is
 reported.  ``device_us``: HIP events around a window of steps with no host read inside (what the device needs per
@@ -21,7 +25,8 @@ its own, one per (mode, variant, K) with K = 10 and 30:
         python tools/vae_train_bench.py --trace VARIANT --mode MODE --steps K
 
 ``--launches DIR --out FILE`` then counts the rows of each run's ``*kernel_trace.csv`` (one row per launch) and writes
-launches per step = (rows at K = 30 - rows at K = 10) / 20, which cancels start-up and data preparation.  ``--out``
+launches per step = (rows at K = 30 - rows at K = 10) / 20, which cancels start-up and data preparation (and the same
+for the rows of libqce.so's own kernels, whose names begin with k_).  ``--out``
 replaces the lines of the kind it measured and keeps the others, so timing and launch counts share one file.
 """
 import argparse
@@ -38,6 +43,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 N, L, LAYERS, BATCH, N_TRAIN = 64, 16, 4, 200, 8000
 SNRS = [-10, -5, 0, 5, 10, 15, 20]
 MODES = {"noisy": 1, "real": 3}
+VARIANTS = ("fused", "composed", "step")
 
 
 _LEVELS = {}
@@ -102,9 +108,24 @@ class Stepper:
         self.t = t if t is not None else observe.encoder_features(h, N, True).reshape(-1, 2 * N)  # 'noisy': the channel
         self.snr32 = None if self.snr is None else self.snr.float()
         self.drawn = 0
+        self.slot = 0  # 'step': entries of the trainer's loss record written since the last read
+
+    def end_window(self, read):
+        """'step': the one host read of a window of steps (the losses and skip flags of the steps since the last)."""
+        if self.variant == "step":
+            if read and self.slot:
+                self.est._fused_read(min(self.slot, self.vae.FUSED_STEP_SLOTS))
+            self.slot = 0
 
     def step(self, read):
         torch, est = self.torch, self.est
+        if self.variant == "step":
+            idx = torch.randperm(N_TRAIN, generator=self.gen, device=self.dev)[:BATCH].to(torch.int32)
+            est._fused_step(self.x, self.t, snr_db=self.snr, index=idx, seed=0, row_offset=self.drawn,
+                            slot=self.slot % self.vae.FUSED_STEP_SLOTS, max_batch=BATCH)
+            self.drawn += BATCH
+            self.slot += 1
+            return
         self.opti.zero_grad()
         idx = torch.randperm(N_TRAIN, generator=self.gen, device=self.dev)[:BATCH]
         xb = self.x.index_select(0, idx)
@@ -136,6 +157,7 @@ def window(st, n, read):
         t0 = time.perf_counter()
         for _ in range(n):
             st.step(True)
+        st.end_window(True)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e6 / n
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -144,6 +166,7 @@ def window(st, n, read):
         st.step(False)
     e1.record()
     torch.cuda.synchronize()
+    st.end_window(False)
     return e0.elapsed_time(e1) * 1e3 / n
 
 
@@ -164,26 +187,32 @@ def count_launches(root, ks=(10, 30)):
     """Launches per step from the kernel traces under root/MODE_VARIANT_K (see the module docstring)."""
     import csv
     import glob
+    import re
     out = []
     for mode in MODES:
-        for v in ("fused", "composed"):
-            n = {}
+        for v in VARIANTS:
+            n, lib = {}, {}
+            if not any(os.path.isdir(os.path.join(root, f"{mode}_{v}_{k}")) for k in ks):
+                continue  # a variant that was not traced
             for k in ks:
                 f = glob.glob(os.path.join(root, f"{mode}_{v}_{k}", "**", "*kernel_trace.csv"), recursive=True)
                 if len(f) != 1:
                     raise SystemExit(f"expected one kernel trace under {root}/{mode}_{v}_{k}, found {len(f)}")
                 with open(f[0]) as fh:
-                    n[k] = sum(1 for _ in csv.DictReader(fh))
+                    names = [r.get("Kernel_Name", "") for r in csv.DictReader(fh)]
+                n[k] = len(names)
+                lib[k] = sum(1 for name in names if re.search(r"\bk_[a-z0-9_]+", name))  # libqce.so's kernels: k_*
             out.append(dict(bench="vae_train_launches", mode=mode, variant=v, N=N, L=L, n_layers=LAYERS, batch=BATCH,
                             **{f"launches_{k}_steps": n[k] for k in ks},
-                            launches_per_step=(n[ks[1]] - n[ks[0]]) / (ks[1] - ks[0])))
+                            launches_per_step=(n[ks[1]] - n[ks[0]]) / (ks[1] - ks[0]),
+                            library_launches_per_step=(lib[ks[1]] - lib[ks[0]]) / (ks[1] - ks[0])))
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--trace", choices=("fused", "composed"), default=None)
+    ap.add_argument("--trace", choices=VARIANTS, default=None)
     ap.add_argument("--mode", choices=tuple(MODES), default="noisy")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--launches", default=None, help="directory of kernel-trace runs MODE_VARIANT_K to count")
@@ -202,15 +231,17 @@ def main():
         st = Stepper(a.mode, a.trace)
         for _ in range(a.steps):
             st.step(False)
+        st.end_window(False)
         torch.cuda.synchronize()
         return
     lines = []
     for mode in MODES:
-        sts = {v: Stepper(mode, v) for v in ("fused", "composed")}
+        sts = {v: Stepper(mode, v) for v in VARIANTS}
         n = {}
         for v, st in sts.items():
             for _ in range(30):
                 st.step(True)
+            st.end_window(True)
             n[v] = max(10, int(np.ceil(a.window_seconds * 1e6 / window(st, 50, True))))
         res = {v: {"device_us": [], "step_us": []} for v in sts}
         for _ in range(a.windows):
